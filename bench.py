@@ -13,6 +13,12 @@ collective on the rollout path (weak scaling); barrier + max-over-ranks timing.
 Rank 0 prints ONE JSON line. `python bench.py --gpus N` (N > 1) outside a launcher starts
 `torch.distributed.run --nproc-per-node N` on this script as a child process (before any GPU
 call) and exits with its return code; under a launcher WORLD_SIZE must equal --gpus.
+
+A plain run sets up, warms up, times --steps steps (exactly that many), writes the rollout's outputs
+after the last of them if --dump-outputs DIR is given, and prints the line. --full adds every other
+leg after the headline (per-kernel timers + roofline, the exact-fp32 pass, rollout + training, the
+other BASELINE configurations, config 4, the rocprofv3 PMC passes, the CPU baseline); each of them
+has a --no-* switch. The inputs are seeded: the same arguments give the same outputs on every run.
 """
 import argparse
 import importlib
@@ -33,6 +39,10 @@ METRIC = "env-steps/sec (routing, --netmon, 20-node graphs) at 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 F32_MFMA_PEAK_TFS = 157.3  # MI355X_MICROARCH.md: f32-input MFMA dense peak
 F16_MFMA_PEAK_TFS = 16 * 157.3  # MI355X_MICROARCH.md: BF16/F16 dense = 16x the f32-input MFMA rate
+# the legs beyond the headline (each has a --no-<leg> switch); they run only with --full
+LEGS = ("kernel_timers", "f32_compare", "train", "extras", "config4", "pmc", "cpu_baseline")
+DUMP_ENVS = 256  # --dump-outputs: envs sampled from the per-env arrays too large to write whole
+DUMP_SEED = 20  # ... by numpy's default_rng(DUMP_SEED)
 
 
 def parse():
@@ -83,9 +93,22 @@ def parse():
                    help="skip the same-run rocprofv3 PMC passes (HBM bytes of DQN layer 1 and k_env_step)")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--pmc-order", default=None, help=argparse.SUPPRESS)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every other leg (per-kernel timers and roofline, exact-fp32 "
+                        "pass, rollout + training, the other BASELINE configurations, config 4, the PMC passes, the "
+                        "CPU baseline), each unless its --no-* switch is given; without --full none of them runs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the rollout holds after its last timed step (joint "
+                        "observation, reward, done, actions, NetMon state) as DIR/<name>.npy")
     p.add_argument("--cpu-envs", type=int, default=1024)
     p.add_argument("--cpu-steps", type=int, default=50, help="one full episode (includes its reset)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: set up, warm up, time --steps steps, print the line
+        for leg in LEGS:
+            setattr(args, "no_" + leg, True)
+    return args
 
 
 def pmc_traffic(tag, build_src=None):
@@ -504,6 +527,43 @@ def measure_config4(args, gm, M, W, P, RO, timed_region, dev, world, rank):
     return out
 
 
+def dump_outputs(out_dir, ro, rank):
+    """--dump-outputs: what a caller of the rollout holds after the last timed step, as float32 .npy files.
+    reward, done and actions [n_env, A] whole (the groups' envs in seed order); the joint observation
+    [n, A, obs_dim + graph features] and the NetMon state [n, N, state] of a fixed sample of n envs
+    (default_rng(DUMP_SEED) over the GPU's envs, sorted; their indices in env_index). Rank r > 0 of a
+    multi-GPU run writes <name>_rank<r>.npy (its own env shard)."""
+    import numpy as np
+
+    torch.cuda.synchronize()
+    per = ro.n_env // ro.groups
+    w0 = ro.wenvs[0]
+    has_netmon = hasattr(w0, "netmon")
+    row_bytes = 4 * w0.env.n_data * (w0.obs_dim if has_netmon else w0.env.obs_dim)
+    if has_netmon:
+        row_bytes += 4 * w0.env.n_nodes * w0.netmon.get_state_size()
+    n = max(1, min(ro.n_env, DUMP_ENVS, (48 << 20) // row_bytes))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(ro.n_env, size=n, replace=False))
+    out = {"env_index": idx.astype(np.float32), "obs": [], "netmon_state": [], "reward": [], "done": [], "actions": []}
+    with torch.no_grad():
+        for g, (env, wenv, pol) in enumerate(zip(ro.envs, ro.wenvs, ro.policies)):
+            sel = torch.as_tensor(idx[(idx >= g * per) & (idx < (g + 1) * per)] - g * per, device=env.reward.device)
+            out["obs"].append(wenv.obs.index_select(0, sel).float().cpu().numpy())
+            if has_netmon:
+                out["netmon_state"].append(wenv.current_netmon_state.index_select(0, sel).float().cpu().numpy())
+            out["reward"].append(env.reward.float().cpu().numpy())
+            out["done"].append(env.done.float().cpu().numpy())
+            out["actions"].append(pol.actions.float().cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, v in out.items():
+        if isinstance(v, list):
+            if not v:
+                continue
+            v = np.concatenate(v)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def launch_ranks(args, argv=None):
     """--gpus N > 1 without a launcher: run N ranks of this script under torch.distributed.run as a
     CHILD process (nothing here has touched the GPU; no exec from this process) and return its exit
@@ -580,19 +640,23 @@ def main():
 
     def timed_region(warmup, steps, timers, ro=ro, graph=0):
         """W warmup steps, then untimed steps up to the episode phase where the FIRST timed step
-        (graph: replay) ends an episode, so the K timed steps always contain ceil(K / episode)
-        topology resets + NetMon start-ups (at the reference's rate or above, whatever K is)."""
+        (graph: replay) ends an episode, so K timed steps contain (K - g) // episode + 1 topology
+        resets + NetMon start-ups (g: the graph length, 1 when eager; at the reference's rate or
+        above). Exactly `steps` steps are timed: whole graph replays first, then the steps left
+        over (steps % graph) as eager launches; fewer steps than one graph run eagerly."""
         EP = args.episode_steps
+        if graph and steps < graph:
+            graph = 0
         g = graph or 1
+        n_replayed = steps // graph * graph if graph else 0
         with torch.no_grad():
             ro.reset()
             # graph replays start at multiples of the captured length: warm up to one
-            for _ in range(-(-warmup // graph) * graph if graph else warmup):
+            for _ in range(max(1, -(-warmup // graph)) * graph if graph else warmup):
                 ro.step()
             if graph:
                 # capture after the eager warmup (packed weights, scratch buffers exist), then
-                # one untimed replay; the timed loop replays steps/graph graphs
-                assert steps % graph == 0, "--steps must be a multiple of --graph"
+                # one untimed replay; the timed loop replays steps // graph graphs
                 ro.capture(graph, per_group=not args.graph_single)
                 ro.run(graph)
             while ro.ep != EP - g:  # position: the first timed step (replay) triggers a reset
@@ -605,10 +669,9 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if graph:
-                ro.run(steps)
-            else:
-                for _ in range(steps):
-                    ro.step()
+                ro.run(n_replayed)
+            for _ in range(steps - n_replayed):
+                ro.step()
             t_issue = time.perf_counter() - t0  # host time to enqueue the steps
             torch.cuda.synchronize()
             if world > 1:
@@ -616,7 +679,8 @@ def main():
             elapsed = time.perf_counter() - t0
             prof, L.PROF = L.PROF, None
             state["host_ms_per_step"] = 1e3 * t_issue / steps
-            state["resets"] = -(-steps // EP)
+            state["resets"] = (steps - g) // EP + 1
+            state["graph"] = graph
         el = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else dev)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -629,6 +693,9 @@ def main():
     elapsed, prof = timed_region(args.warmup, args.steps, timers and G == 1 and not args.graph, graph=args.graph)
     host_ms = state["host_ms_per_step"]
     resets = state["resets"]
+    graph_used = state["graph"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ro, rank)
     if timers and (G > 1 or args.graph):
         # per-kernel durations from the same rollout as ONE group (kernels not overlapped), for
         # the roofline fields and the rocprofv3 cross-check (tools/gpu_check.sh prof: --groups 1)
@@ -767,7 +834,7 @@ def main():
                        "n_env_per_gpu": B, "n_nodes": N, "n_data": A, "netmon_iterations": K,
                        "gemm_form": L.GEMM_MODE,
                        "parallelism": f"dp{world} (env shards, no rollout collective)",
-                       "stream_groups": G, "graph_steps": args.graph,
+                       "stream_groups": G, "graph_steps": graph_used,
                        "resets_in_window": resets},
             "host_enqueue_ms_per_step": round(host_ms, 4),
             "roofline": roof, "roofline_hbm": roof_hbm or None, "cpu_baseline": cpu, "f32_exact_gemms": f32cmp, "rollout_train": train,

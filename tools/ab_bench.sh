@@ -7,7 +7,7 @@ reps=$1; shift
 for i in $(seq "$reps"); do
   for name in "$@"; do
     lib=""; [ "$name" != default ] && lib=graph-marl_amd/lib/$name/libgraphmarl_amd.so
-    GM_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --steps 100 --no-f32-compare --no-extras --no-pmc \
+    GM_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 100 --no-f32-compare --no-extras --no-pmc \
         --train-steps 4 > gpurun_out/ab_bench.tmp 2>&1 || exit $?
     python - "$name" >> gpurun_out/ab_bench.log <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 for i in $(seq "$1"); do
   for tree in ab_old .; do
-    timeout -k 10 300 python $tree/bench.py --no-cpu-baseline --steps 100 --no-f32-compare --no-extras --no-pmc \
+    timeout -k 10 300 python $tree/bench.py $(grep -q -e --full $tree/bench.py && echo --full) --no-cpu-baseline --steps 100 --no-f32-compare --no-extras --no-pmc \
         --train-steps 4 > gpurun_out/ab_code.tmp 2>&1 || exit $?
     python - "$tree" >> gpurun_out/ab_code.log <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ for i in $(seq ${ROUNDS:-2}); do
   for v in "$@"; do
     lib=graph-marl_amd/lib/$v/libgraphmarl_amd.so
     [ "$v" = default ] && lib=
-    GM_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline $([ -n "$EXTRAS" ] || echo --no-extras) --no-pmc --no-f32-compare \
+    GM_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline $([ -n "$EXTRAS" ] || echo --no-extras) --no-pmc --no-f32-compare \
         ${BENCH_ARGS:---steps 100 --train-steps 5} > gpurun_out/bench_ab.tmp 2>&1 || exit $?
     python - "$v" >> gpurun_out/bench_ab.log <<'PY'
 import json, sys

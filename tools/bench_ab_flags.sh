@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 for i in $(seq ${ROUNDS:-2}); do
   for f in "$@"; do
-    timeout -k 10 200 python bench.py --no-cpu-baseline --no-pmc --no-extras --steps ${STEPS:-200} --no-train \
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-pmc --no-extras --steps ${STEPS:-200} --no-train \
         --no-f32-compare $f > gpurun_out/abf.tmp 2>&1 || exit $?
     python - "$f" >> gpurun_out/abf.log <<'PY'
 import json, sys

@@ -27,20 +27,20 @@ for s in "$@"; do
         sl20) step sl20_bench 600 python graph-marl_amd/sl.py --bench --n-nodes 20 --batch-size 1024 --sequence-length 4 \
                 --netmon-iterations 3 --iterations 20 --warmup 3 || exit $? ;;
         dist2) GM_BENCH_SHARE_GPU=1 step dist2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 20 --warmup 5 \
+                --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 20 --warmup 5 \
                 --no-cpu-baseline || exit $? ;;
         gemm) X3_TILES=${X3_TILES:--1,1,2,3,4,5} step gemm 300 python tools/gemm_bench.py || exit $? ;;
         models) step models_tests 600 python -m pytest tests/test_models_gpu.py -x -q --tb=short --timeout=300 -p no:cacheprovider || exit $? ;;
         fused) step fused_tests 600 python -m pytest tests/test_fused_gpu.py -x -q --tb=short --timeout=300 -p no:cacheprovider || exit $? ;;
         rollout) step rollout_tests 600 python -m pytest tests/test_rollout_gpu.py -x -q --tb=short --timeout=300 -p no:cacheprovider || exit $? ;;
-        benchg) step bench_graph 300 python bench.py --no-cpu-baseline --steps 100 --graph ${GRAPH:-2} --no-train || exit $? ;;
-        benchg0) step bench_eager 300 python bench.py --no-cpu-baseline --steps 100 --no-train || exit $? ;;
-        benchf32) GM_GEMM=f32 step bench_f32 300 python bench.py --no-cpu-baseline --steps 100 || exit $? ;;
-        bench) step bench 600 python bench.py || exit $? ;;
-        benchst) step bench_stagger 300 python bench.py --no-cpu-baseline --steps 100 --stagger || exit $? ;;
-        benchq) step bench 300 python bench.py --no-cpu-baseline --steps 100 || exit $? ;;
+        benchg) step bench_graph 300 python bench.py --full --no-cpu-baseline --steps 100 --graph ${GRAPH:-2} --no-train || exit $? ;;
+        benchg0) step bench_eager 300 python bench.py --full --no-cpu-baseline --steps 100 --no-train || exit $? ;;
+        benchf32) GM_GEMM=f32 step bench_f32 300 python bench.py --full --no-cpu-baseline --steps 100 || exit $? ;;
+        bench) step bench 600 python bench.py --full || exit $? ;;
+        benchst) step bench_stagger 300 python bench.py --full --no-cpu-baseline --steps 100 --stagger || exit $? ;;
+        benchq) step bench 300 python bench.py --full --no-cpu-baseline --steps 100 || exit $? ;;
         prof) step prof 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d gpurun_out/prof -o bench \
-                  -- python bench.py --steps 100 --groups 1 --no-cpu-baseline --no-pmc --no-train --no-f32-compare --no-extras --graph 0 || exit $? ;;
+                  -- python bench.py --full --steps 100 --groups 1 --no-cpu-baseline --no-pmc --no-train --no-f32-compare --no-extras --graph 0 || exit $? ;;
         pmc) step pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d gpurun_out/pmc -o fetch \
                  -- python bench.py --steps 20 --warmup 5 --groups 1 --no-cpu-baseline --no-pmc --no-kernel-timers --no-train --no-f32-compare --no-extras --graph 0 || exit $?
              step pmc_write 600 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d gpurun_out/pmc -o write \

@@ -8,5 +8,5 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d gpu
     -- python graph-marl_amd/sl.py --bench --n-nodes 100 --batch-size 8192 --sequence-length 8 --netmon-iterations 1 \
     --iterations 3 --warmup 1 > gpurun_out/slprof/run.log 2>&1 || exit $?
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T --output-format csv -d gpurun_out/tprof -o t \
-    -- python bench.py --steps 4 --warmup 2 --graph 0 --no-extras --no-cpu-baseline --no-f32-compare --no-kernel-timers \
+    -- python bench.py --full --steps 4 --warmup 2 --graph 0 --no-extras --no-cpu-baseline --no-f32-compare --no-kernel-timers \
     --no-pmc --train-steps 4 > gpurun_out/tprof/b.log 2>&1

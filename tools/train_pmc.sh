@@ -7,7 +7,7 @@ mkdir -p gpurun_out/tpmc
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 300 rocprofv3 --pmc $c -T --output-format csv -d gpurun_out/tpmc -o $c \
-        -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-f32-compare --no-pmc \
+        -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-f32-compare --no-pmc \
         --no-extras --graph 0 --train-steps 2 > gpurun_out/tpmc/bench_$c.log 2>&1 || exit $?
 done
 python - <<'PY' > gpurun_out/tpmc/summary.txt

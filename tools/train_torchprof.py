@@ -37,6 +37,6 @@ def wrapped(*a, **k):
 
 
 T.dqn_update = wrapped
-sys.argv = [sys.argv[0], "--no-cpu-baseline", "--no-f32-compare", "--steps", "10", "--warmup", "2", "--train-steps",
+sys.argv = [sys.argv[0], "--full", "--no-cpu-baseline", "--no-f32-compare", "--steps", "10", "--warmup", "2", "--train-steps",
             "3", "--no-kernel-timers"]
 bench.main()
