@@ -26,7 +26,7 @@ EXPORTS = [
     "gm_last_error", "gm_version", "gm_env_create", "gm_env_destroy", "gm_env_dims", "gm_env_reset",
     "gm_env_step", "gm_env_observe", "gm_env_topology", "gm_env_final_info", "gm_policy_egreedy", "gm_env_policy_step",
     "gm_env_get_state", "gm_env_set_state", "gm_build_seed_list", "gm_mp_aggregate", "gm_mp_aggregate_rows", "gm_mp_aggregate_bwd", "gm_leaky_bwd", "gm_netmon_readout",
-    "gm_netmon_readout_bwd", "gm_lstm_pointwise", "gm_lstm_pointwise_bwd", "gm_linear_f32", "gm_gemm_f32",
+    "gm_netmon_readout_bwd", "gm_netmon_readout_bwd_sym", "gm_lstm_pointwise", "gm_lstm_pointwise_bwd", "gm_linear_f32", "gm_gemm_f32",
     "gm_simple_create", "gm_simple_destroy", "gm_simple_reset", "gm_simple_step",
     "gm_simple_observe", "gm_simple_policy_egreedy", "gm_simple_get_state", "gm_env_set_topology",
     "gm_policy_shortest_path", "gm_env_first_hops", "gm_routing_node_encoder", "gm_gemm_x3", "gm_gemm_x3_head", "gm_absmax_scale", "gm_absmax_scale_rows", "gm_gemm_x3_wgrad", "gm_gemm_x3_wgrad2", "gm_absmax_finish",
@@ -38,7 +38,8 @@ EXPORTS = [
     "gm_step_mse_bwd",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
-TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form"]
+TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
+                  "gm_last_kernel"]
 
 # Arithmetic form of the fused rollout GEMMs (graph-marl_amd/fused.py): "x3" = split-f16
 # MFMA with fp32 accumulation (default), "f32" = exact fp32 MFMA. GM_GEMM=f32 selects the
@@ -176,6 +177,7 @@ def lib():
         "gm_step_mse_blocks": [i64],
         "gm_step_mse": [vp, vp, i64, i32, vp, vp],
         "gm_step_mse_bwd": [vp, vp, i64, i32, vp, C.c_float, vp, vp],
+        "gm_netmon_readout_bwd_sym": [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp],
     }
     for name, at in newer.items():
         if hasattr(L, name) or not os.environ.get("GM_LIB"):
@@ -186,6 +188,8 @@ def lib():
         L.gm_build_info.restype = C.c_char_p
     if hasattr(L, "gm_gemm_form"):
         L.gm_gemm_form.restype = C.c_char_p
+    if hasattr(L, "gm_last_kernel"):
+        L.gm_last_kernel.restype = C.c_char_p
     _lib = L
     return L
 
@@ -221,6 +225,12 @@ def build_info():
     except OSError:
         d["matches_tree"] = None
     return d
+
+
+def last_kernel():
+    """Diagnostic (gm_last_kernel): the kernel this thread's most recent NetMon dispatcher call launched.
+    For the dispatch tests; the product never reads it."""
+    return lib().gm_last_kernel().decode()
 
 
 def check(rc):

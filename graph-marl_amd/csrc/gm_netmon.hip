@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/graph_marl_amd.h"
+#include "../../include/graph_marl_amd_tuning.h"
 #include "gm_amax.hpp"
 #include "gm_act.hpp"
 
@@ -466,8 +467,15 @@ static int vec_width(int H, long long stride, const void* p) {
     return 1;
 }
 
+// gm_last_kernel (diagnostics, graph_marl_amd_tuning.h): every launch site of the dispatchers below names its
+// kernel first: one host store per call
+static thread_local const char* g_last_kernel = "";
+#define GM_RAN(NAME) (g_last_kernel = (NAME))
+extern "C" const char* gm_last_kernel(void) { return g_last_kernel; }
+
 #define GM_VLAUNCH(KER, V, GRID, ...)                                                                  \
     do {                                                                                               \
+        GM_RAN((V) == 4 ? #KER "<4>" : (V) == 2 ? #KER "<2>" : #KER "<1>");                           \
         if ((V) == 4) hipLaunchKernelGGL(KER<4>, GRID, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
         else if ((V) == 2) hipLaunchKernelGGL(KER<2>, GRID, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
         else hipLaunchKernelGGL(KER<1>, GRID, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);        \
@@ -485,6 +493,8 @@ static int launch_agg(const float* h, const int32_t* nbr, int32_t G, int32_t N, 
         GM_VLAUNCH(k_mp_aggregate3, V, grid, h, nbr, (unsigned)N, (unsigned)(H / V), mode, out, ldh, ldo, (unsigned)total);
         return launched();
     }
+    if (BWD) GM_RAN(V == 4 ? "k_mp_aggregate<bwd,4>" : V == 2 ? "k_mp_aggregate<bwd,2>" : "k_mp_aggregate<bwd,1>");
+    else GM_RAN(V == 4 ? "k_mp_aggregate<fwd,4>" : V == 2 ? "k_mp_aggregate<fwd,2>" : "k_mp_aggregate<fwd,1>");
     if (V == 4) hipLaunchKernelGGL((k_mp_aggregate<BWD, 4>), grid, dim3(256), 0, (hipStream_t)stream, h, nbr, G, N, deg, H, mode, out, ldh, ldo);
     else if (V == 2) hipLaunchKernelGGL((k_mp_aggregate<BWD, 2>), grid, dim3(256), 0, (hipStream_t)stream, h, nbr, G, N, deg, H, mode, out, ldh, ldo);
     else hipLaunchKernelGGL((k_mp_aggregate<BWD, 1>), grid, dim3(256), 0, (hipStream_t)stream, h, nbr, G, N, deg, H, mode, out, ldh, ldo);
@@ -812,6 +822,7 @@ extern "C" int gm_netmon_readout_ld(const float* hf, int64_t ldf, const float* h
     if (V == 4) {
         const long long rows = (long long)G * R;
         const long long blocks = std::min<long long>((rows + 3) / 4, 65536);
+        GM_RAN("k_readout_rows");
         hipLaunchKernelGGL(k_readout_rows, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hf, hp, nbr,
                            agent_node, rows, N, R, deg, H, out, (long long)stride, (long long)ldf, (long long)ldp);
         return launched();
@@ -871,22 +882,28 @@ __global__ __launch_bounds__(1024) void k_readout_bwd_g(const float* __restrict_
     if (dhp) stv<V>(dhp + node * H + off, ap);
 }
 
-extern "C" int gm_netmon_readout_bwd(const float* dout, int64_t stride, const int32_t* nbr, const int32_t* agent_node,
-                                     int32_t G, int32_t N, int32_t R, int32_t deg, int32_t H, float* dhf, float* dhp,
-                                     void* stream) {
+// sym: the caller vouches for a symmetric neighbour table without repeated entries (gm_netmon_readout_bwd_sym);
+// only then may the no-map call take k_readout_bwd_nodes, which is silently wrong on any other table
+static int readout_bwd(const float* dout, int64_t stride, const int32_t* nbr, const int32_t* agent_node, int32_t G,
+                       int32_t N, int32_t R, int32_t deg, int32_t H, float* dhf, float* dhp, bool sym, void* stream) {
     if (!dout || !nbr || G <= 0 || N <= 0 || R <= 0 || deg < 0 || H <= 0)
         return gm_fail(GM_ERR_INVALID_ARG, "gm_netmon_readout_bwd: bad arguments");
     int V = vec_width(H, stride, dout);
     if (dhf) { int v = vec_width(H, H, dhf); V = V < v ? V : v; }
     if (dhp) { int v = vec_width(H, H, dhp); V = V < v ? V : v; }
-    if (!agent_node && R == N && V == 4 && deg <= MAXDEG) {  // every node read out: a gather per node
+    if (!agent_node && R != N)
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_netmon_readout_bwd: R must equal N without agent map");
+    if (sym && !agent_node && V == 4 && deg <= MAXDEG) {  // symmetric table, every node read out: a gather per node
         const long long total = (long long)G * N * (H / 4);
-        if (total + 256 < (1ll << 31))
+        if (total + 256 < (1ll << 31)) {
+            GM_RAN("k_readout_bwd_nodes<unsigned>");
             hipLaunchKernelGGL(k_readout_bwd_nodes<unsigned>, dim3(nblocks(total, 256)), dim3(256), 0,
                                (hipStream_t)stream, dout, (long long)stride, nbr, (long long)G * N, N, deg, H, dhf, dhp);
-        else
+        } else {
+            GM_RAN("k_readout_bwd_nodes<long long>");
             hipLaunchKernelGGL(k_readout_bwd_nodes<long long>, dim3(nblocks(total, 256)), dim3(256), 0,
                                (hipStream_t)stream, dout, (long long)stride, nbr, (long long)G * N, N, deg, H, dhf, dhp);
+        }
         return launched();
     }
     const size_t lds = (size_t)R * (deg + 1) * H * 4;
@@ -894,16 +911,20 @@ extern "C" int gm_netmon_readout_bwd(const float* dout, int64_t stride, const in
     const int S = (lds / 4 <= 48 * 1024 || (H / 4) % 8) ? 4 : 8;
     if (V == 4 && R <= 128 && N <= 128 && deg <= 3 && (H / 4) % S == 0 && lds / S <= 48 * 1024) {
         const int threads = std::min(256, (N * (H / (4 * S)) + 63) / 64 * 64);
-        if (R <= 64)
+        if (R <= 64) {
+            GM_RAN(S == 4 ? "k_readout_bwd_cs<1>/S=4" : "k_readout_bwd_cs<1>/S=8");
             hipLaunchKernelGGL(k_readout_bwd_cs<1>, dim3((unsigned)((long long)G * S)), dim3(threads), lds / S,
                                (hipStream_t)stream, dout, (long long)stride, nbr, agent_node, N, R, deg, H, S, dhf, dhp);
-        else  // up to 128 rows per graph (e.g. every node of a 100-node graph, no agent map)
+        } else {  // up to 128 rows per graph (e.g. every node of a 100-node graph, no agent map)
+            GM_RAN(S == 4 ? "k_readout_bwd_cs<2>/S=4" : "k_readout_bwd_cs<2>/S=8");
             hipLaunchKernelGGL(k_readout_bwd_cs<2>, dim3((unsigned)((long long)G * S)), dim3(threads), lds / S,
                                (hipStream_t)stream, dout, (long long)stride, nbr, agent_node, N, R, deg, H, S, dhf, dhp);
+        }
         return launched();
     }
     if (V == 4 && R <= 64 && deg <= MAXDEG && lds <= 48 * 1024) {
         const int threads = std::min(1024, (N * (H / 4) + 63) / 64 * 64);
+        GM_RAN("k_readout_bwd_lds");
         hipLaunchKernelGGL(k_readout_bwd_lds, dim3(G), dim3(threads), lds, (hipStream_t)stream, dout, (long long)stride,
                            nbr, agent_node, N, R, deg, H, dhf, dhp);
         return launched();
@@ -911,6 +932,7 @@ extern "C" int gm_netmon_readout_bwd(const float* dout, int64_t stride, const in
     if (R <= 64 && deg <= MAXDEG && N * (H / V) <= 1024) {
         const int threads = (N * (H / V) + 63) / 64 * 64;
         hipStream_t st = (hipStream_t)stream;
+        GM_RAN(V == 4 ? "k_readout_bwd_g<4>" : V == 2 ? "k_readout_bwd_g<2>" : "k_readout_bwd_g<1>");
         if (V == 4)
             hipLaunchKernelGGL(k_readout_bwd_g<4>, dim3(G), dim3(threads), 0, st, dout, (long long)stride, nbr,
                                agent_node, N, R, deg, H, dhf, dhp);
@@ -926,6 +948,17 @@ extern "C" int gm_netmon_readout_bwd(const float* dout, int64_t stride, const in
     GM_VLAUNCH(k_readout_bwd, V, dim3(nblocks(total, 256)), dout, (long long)stride, nbr, agent_node, G, N, R, deg, H,
                dhf, dhp);
     return launched();
+}
+
+extern "C" int gm_netmon_readout_bwd(const float* dout, int64_t stride, const int32_t* nbr, const int32_t* agent_node,
+                                     int32_t G, int32_t N, int32_t R, int32_t deg, int32_t H, float* dhf, float* dhp,
+                                     void* stream) {
+    return readout_bwd(dout, stride, nbr, agent_node, G, N, R, deg, H, dhf, dhp, false, stream);
+}
+
+extern "C" int gm_netmon_readout_bwd_sym(const float* dout, int64_t stride, const int32_t* nbr, int32_t G, int32_t N,
+                                         int32_t deg, int32_t H, float* dhf, float* dhp, void* stream) {
+    return readout_bwd(dout, stride, nbr, nullptr, G, N, N, deg, H, dhf, dhp, true, stream);
 }
 
 extern "C" int gm_lstm_pointwise(const float* gates, const float* c, int32_t m, int32_t H, float* h1, float* c1,
@@ -1351,9 +1384,11 @@ extern "C" int gm_lstm_cell_bwd(const gm_lstm_bwd_args* a, void* stream) {
                      a16(b.dc_out, b.ld_dco) && a16(b.bias_part, 4);
     if (vec) {
         const int rl4 = 256 / (H / 4);
+        GM_RAN("k_lstm_cell_bwd4");
         hipLaunchKernelGGL(k_lstm_cell_bwd4, dim3((unsigned)nb), dim3(rl4 * (H / 4)), 0, st, b,
                            reinterpret_cast<unsigned*>(b.dg_scale), reinterpret_cast<unsigned*>(b.dg_max));
     } else {
+        GM_RAN("k_lstm_cell_bwd");
         hipLaunchKernelGGL(k_lstm_cell_bwd, dim3((unsigned)nb), dim3(threads), 0, st, b,
                            reinterpret_cast<unsigned*>(b.dg_scale), reinterpret_cast<unsigned*>(b.dg_max));
     }
@@ -1376,6 +1411,7 @@ extern "C" int gm_qhead_bwd(const float* dq, int64_t ldq, int32_t nq, const floa
     if (cols % 4 == 0 && cols <= 1024 && ((256 / (cols / 4)) * (cols / 4)) % 64 == 0 && a16(wq, ldwq) &&
         a16(y, ldy) && a16(g, ldg) && a16(part_b, cols) && a16(part_wq, cols)) {
         const int rl = 256 / (cols / 4);
+        GM_RAN("k_qhead_bwd4");
         hipLaunchKernelGGL(k_qhead_bwd4, dim3((unsigned)nb), dim3(rl * (cols / 4)), 0, st, dq, (long long)ldq, nq, wq,
                            (long long)ldwq, y, (long long)ldy, (long long)rows, cols, act, g, (long long)ldg, part_b,
                            part_wq, part_bq, rows_per_block, reinterpret_cast<unsigned*>(g_scale));
@@ -1384,6 +1420,7 @@ extern "C" int gm_qhead_bwd(const float* dq, int64_t ldq, int32_t nq, const floa
         return rc;
     }
     const int threads = (cols + 63) / 64 * 64;
+    GM_RAN("k_qhead_bwd");
     hipLaunchKernelGGL(k_qhead_bwd, dim3((unsigned)nb), dim3(threads), 0, st, dq, (long long)ldq, nq, wq,
                        (long long)ldwq, y, (long long)ldy, (long long)rows, cols, act, g, (long long)ldg, part_b,
                        part_wq, part_bq, rows_per_block, reinterpret_cast<unsigned*>(g_scale));

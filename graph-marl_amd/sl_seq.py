@@ -160,11 +160,13 @@ def _backward(p, dR):
     dR = dR.reshape(Ls * M, 4 * H).contiguous()
 
     # ---- readout, every step: dh_final of node v is row v's first segment of dR (read in place by the
-    # cell backward, ld 4H); dh_prev gathered from the neighbours' segments (gm_netmon_readout_bwd, no agent map)
+    # cell backward, ld 4H); dh_prev gathered from the neighbours' segments. The supervised driver's tables
+    # are the routing env's own (sl.py's dataset clones env.nbr: symmetric, no repeated entries), so this caller opts
+    # in to the gather kernel (gm_netmon_readout_bwd_sym); gm_netmon_readout_bwd takes any table
     dhp = torch.empty(Ls * M, H, device=dev)
     for t in range(Ls):
-        L.check(lib.gm_netmon_readout_bwd(dR[t * M:(t + 1) * M].data_ptr(), 4 * H, nbr.data_ptr(), None, B, N, N, deg,
-                                          H, None, dhp[t * M:(t + 1) * M].data_ptr(), L.stream_ptr()))
+        L.check(lib.gm_netmon_readout_bwd_sym(dR[t * M:(t + 1) * M].data_ptr(), 4 * H, nbr.data_ptr(), B, N, deg,
+                                              H, None, dhp[t * M:(t + 1) * M].data_ptr(), L.stream_ptr()))
 
     # ---- LSTM cells, per step, in reverse ----
     S, act, Z = p.S, p.act, p.Z

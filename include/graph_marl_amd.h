@@ -287,13 +287,21 @@ int gm_mp_aggregate_bwd(const float* dout, const int32_t* nbr, int32_t n_graphs,
 int gm_netmon_readout(const float* h_final, const float* h_prev, const int32_t* nbr, const int32_t* agent_node,
                       int32_t n_graphs, int32_t n_nodes, int32_t n_rows, int32_t deg, int32_t hidden, float* out,
                       int64_t out_stride, void* stream);
-/* Its backward: dh_final[v] / dh_prev[u] = the sums of the dout segments that read them (either output
- * nullable). Without an agent map (agent_node NULL, n_rows = n_nodes: every node read out, config 5) the
- * neighbour table must be symmetric (u in nbr(v) <=> v in nbr(u): the routing graphs are), and dh_prev[u] is
- * gathered from u's neighbours' rows (ascending, the same fp32 sums as the general form). */
+/* Its backward: dh_final[v] / dh_prev[u] = the sums of the dout segments that read them, in ascending (row,
+ * segment) order (either output nullable; nodes nobody reads get zeros). Correct for any neighbour table
+ * (asymmetric, unsorted, repeated entries, -1 holes), with or without an agent map. */
 int gm_netmon_readout_bwd(const float* dout, int64_t dout_stride, const int32_t* nbr, const int32_t* agent_node,
                           int32_t n_graphs, int32_t n_nodes, int32_t n_rows, int32_t deg, int32_t hidden,
                           float* dh_final, float* dh_prev, void* stream);
+/* The same without an agent map (every node read out, n_rows = n_nodes: config 5) for callers that KNOW their
+ * neighbour table is symmetric and free of repeated entries (u is in nbr(v) exactly once <=> v is in nbr(u)
+ * exactly once: the routing env's graphs are): dh_prev[u] is gathered from the rows of u's neighbours, in the
+ * order of u's list (on an ascending list the same fp32 sums as gm_netmon_readout_bwd). On any other table
+ * the result is wrong without an error: use gm_netmon_readout_bwd. Rows that are not 16-byte lanes (hidden
+ * % 4, stride % 4 or a base not 16-byte aligned) or deg > 8 take gm_netmon_readout_bwd's kernels. */
+int gm_netmon_readout_bwd_sym(const float* dout, int64_t dout_stride, const int32_t* nbr, int32_t n_graphs,
+                              int32_t n_nodes, int32_t deg, int32_t hidden, float* dh_final, float* dh_prev,
+                              void* stream);
 /* LSTM gate math: gates [M, 4H] pre-activations (i,f,g,o, biases included), c [M, H]
  * -> h_new, c_new [M, H]; saves sigmoid/tanh activations in act [M, 4H] if non-NULL. */
 int gm_lstm_pointwise(const float* gates, const float* c, int32_t m, int32_t hidden, float* h_new, float* c_new,

@@ -34,6 +34,11 @@ int gm_gemm_set_dgrad(int32_t form);
  * with the A operand's low piece scaled by 2^12 in every kernel (the only form since round 5);
  * diag = 0 for the product build, 30 for the k-step stamp build (tools/stamp_bench.py). */
 const char* gm_gemm_form(void);
+/* Diagnostic: the kernel the most recent call on this thread of gm_netmon_readout[_ld], gm_netmon_readout_bwd[_sym],
+ * gm_mp_aggregate[_rows|_bwd], gm_lstm_cell_bwd or gm_qhead_bwd launched, as a string literal such as
+ * "k_readout_bwd_cs<2>/S=8" ("" before the first such call). One host store per call; the tests of the
+ * dispatch thresholds read it (tests/test_netmon_paths_gpu.py), the product never does. */
+const char* gm_last_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,11 @@ def _dgrad_case(M, T, S, FU, L, m, n, k, split):
 
 @pytest.mark.parametrize("rows,cols,nq", [(100000, 256, 4), (777, 32, 3), (5, 64, 1), (300, 100, 2)])
 def test_qhead_bwd_vs_torch(rows, cols, nq):
+    qhead_bwd_case(rows, cols, nq)
+
+
+def qhead_bwd_case(rows, cols, nq):
+    """gm_qhead_bwd against torch autograd (also run at the dispatch edges by test_netmon_paths_gpu.py)."""
     M, T, S, FU, L = mods()
     torch.manual_seed(rows)
     z = torch.randn(rows, cols, device="cuda", requires_grad=True)
@@ -148,13 +153,20 @@ def test_qhead_bwd_vs_torch(rows, cols, nq):
 def test_lstm_cell_bwd_vs_autograd(mean, H):
     """gm_lstm_cell_bwd with every gradient source (two plain dh, the transposed aggregate of dm,
     masked external dh / dc, plain dc) against torch autograd of nn.LSTMCell gate math."""
-    M, T, S, FU, L = mods()
     gm = importlib.import_module("graph-marl_amd")
-    torch.manual_seed(H + mean)
     B, N = 48, 20
     env = gm.Routing(gm.Network(N, random_topology=True, excluded_seeds=gm.EVAL_SEEDS), 20, n_env=B, seed=1)
     env.reset()
-    nbr = env.nbr.contiguous()
+    lstm_cell_bwd_case(env.nbr.contiguous(), B, N, H, mean)
+
+
+def lstm_cell_bwd_case(nbr, B, N, H, mean, ld_dg=None):
+    """gm_lstm_cell_bwd on B graphs of N nodes (symmetric degree-3 table nbr) against torch autograd; ld_dg: the
+    row stride of the gate gradients (default 4H; the padding must stay untouched). Also run at the dispatch
+    edges by test_netmon_paths_gpu.py."""
+    M, T, S, FU, L = mods()
+    torch.manual_seed(H + mean)
+    ld_dg = ld_dg or 4 * H
     m = B * N
     pre = torch.randn(m, 4 * H, device="cuda", requires_grad=True)
     c = torch.randn(m, H, device="cuda", requires_grad=True)
@@ -186,18 +198,20 @@ def test_lstm_cell_bwd_vs_autograd(mean, H):
     a.ext_mask, a.rows_per_sample = em.data_ptr(), N
     a.dc, a.ld_dc = dcp.data_ptr(), H
     a.m, a.hidden = m, H
-    dg = torch.empty(m, 4 * H, device="cuda")
+    dgb = torch.full((m, ld_dg), float("nan"), device="cuda")
+    dg = dgb[:, :4 * H]
     dco = torch.empty(m, H, device="cuda")
     part = torch.empty((m + 63) // 64, 4 * H, device="cuda")
     sc = torch.empty(1, device="cuda")
     mx = torch.zeros(1, device="cuda")
-    a.dgates, a.ld_dg, a.dc_out, a.ld_dco = dg.data_ptr(), 4 * H, dco.data_ptr(), H
+    a.dgates, a.ld_dg, a.dc_out, a.ld_dco = dgb.data_ptr(), ld_dg, dco.data_ptr(), H
     a.bias_part, a.rows_per_block, a.dg_scale, a.dg_max = part.data_ptr(), 64, sc.data_ptr(), mx.data_ptr()
     L.check(L.lib().gm_lstm_cell_bwd(C.byref(a), L.stream_ptr()))
     assert _rel(dg, pre.grad) < 2e-6
     assert _rel(dco, c.grad) < 2e-6
     assert _rel(part.sum(0), pre.grad.sum(0)) < 1e-5
     assert mx.item() == dg.abs().max().item()
+    assert torch.isnan(dgb[:, 4 * H:]).all()
 
 
 def _golden_seq(g, dev, netmon, RBm, state0=None):
