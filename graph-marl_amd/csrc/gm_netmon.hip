@@ -1711,6 +1711,19 @@ __global__ __launch_bounds__(256) void k_lnlstm_bwd(const float* __restrict__ Gi
     }
 }
 
+// h' of a GRU cell from its pre-activations a_r, a_z, a_nx, a_nh and the state h, in ONE operation order for
+// every kernel that computes it (gm_gru_cell_fwd gives gm_gru_pointwise's bits): the tanh argument is one fma,
+// the blend two products and a sum, whatever the surrounding code would let the compiler contract or pack.
+__device__ __forceinline__ float gru_gate(float ar, float az, float anx, float anh, float h, float& r, float& z,
+                                          float& n) {
+#pragma clang fp contract(off)
+    r = sig_f(ar);
+    z = sig_f(az);
+    n = tanh_f(fmaf(r, anh, anx));
+    const float t0 = (1.f - z) * n, t1 = z * h;
+    return t0 + t1;
+}
+
 // GRU cell gate math (torch.nn.GRUCell, gate order r, z, n): gi = x W_ih^T + b_ih, gh = h W_hh^T + b_hh
 // ([m][3H] each, strided), r = sigma(gi_r + gh_r), z = sigma(gi_z + gh_z), n = tanh(gi_n + r gh_n),
 // h' = (1 - z) n + z h. One thread per (row, unit).
@@ -1724,9 +1737,9 @@ __global__ __launch_bounds__(256) void k_gru_pw(const float* __restrict__ gi, lo
     const int u = (int)(t - row * H);
     const float* a = gi + row * ldgi;
     const float* b = gh + row * ldgh;
-    const float r = sig_f(a[u] + b[u]), z = sig_f(a[H + u] + b[H + u]);
-    const float n = tanh_f(a[2 * H + u] + r * b[2 * H + u]);
-    y[row * ldy + u] = (1.f - z) * n + z * h[row * ldh + u];
+    float r, z, n;
+    y[row * ldy + u] =
+        gru_gate(a[u] + b[u], a[H + u] + b[H + u], a[2 * H + u], b[2 * H + u], h[row * ldh + u], r, z, n);
 }
 
 // Backward of k_gru_pw: dn = dh' (1 - z), dz = dh' (h - n), dh = dh' z; dn_pre = dn (1 - n^2);
@@ -1758,6 +1771,161 @@ __global__ __launch_bounds__(256) void k_gru_bwd(const float* __restrict__ gi, l
     dgh[row * lddgh + H + u] = dzp;
     dgh[row * lddgh + 2 * H + u] = dnp * r;
     dh[row * lddh + u] = g * z;
+}
+
+// GRU cell of the sequence-batched training path (gm_gru_cell_fwd): P = [a_r | a_z | a_nx | a_nh] is the one
+// [x | h] GEMM's output on the four-tile weight (fused.pack_gru's blocks in natural order, biases included);
+// the same arithmetic as k_gru_pw per (row, unit), V consecutive units per thread; P becomes G = [r | z | n |
+// a_nh], what k_gru_cell_bwd reads.
+template <int V>
+__global__ __launch_bounds__(256) void k_gru_cell_fwd(float* __restrict__ P, long long ldp,
+                                                      const float* __restrict__ h, long long ldh, int M, int H,
+                                                      float* __restrict__ y, long long ldy) {
+    const int HV = H / V;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)M * HV) return;
+    const long long row = t / HV;
+    const int u = (int)(t - row * HV) * V;
+    float* a = P + row * ldp + u;
+    const Vec<V> ar = ldv<V>(a), az = ldv<V>(a + H), anx = ldv<V>(a + 2 * H), anh = ldv<V>(a + 3 * H);
+    const Vec<V> hv = ldv<V>(h + row * ldh + u);
+    Vec<V> r4, z4, n4, o4;
+#pragma unroll
+    for (int e = 0; e < V; e++) {
+        float r, z, n;
+        o4.v[e] = gru_gate(ar.v[e], az.v[e], anx.v[e], anh.v[e], hv.v[e], r, z, n);
+        r4.v[e] = r;
+        z4.v[e] = z;
+        n4.v[e] = n;
+    }
+    stv<V>(y + row * ldy + u, o4);
+    stv<V>(a, r4);
+    stv<V>(a + H, z4);
+    stv<V>(a + 2 * H, n4);
+}
+
+// transposed (I + A) aggregate of dm for row r, unit u (gm_gru_cell_bwd): members of r's node in ascending id,
+// each scaled by 1 / |{n} U nbr(n)| for mean (k_lstm_cell_bwd's loop)
+template <int V>
+__device__ __forceinline__ void gru_dm_add(const gm_gru_bwd_args& a, long long r, int u, Vec<V>& g) {
+    const int N = a.n_nodes;
+    const long long gr = r / N;
+    const int n = (int)(r - gr * N);
+    int mem[MAXDEG + 1];
+    const int cnt = members(a.nbr + r * a.deg, a.deg, n, mem);
+    for (int q = 0; q < cnt; q++) {
+        Vec<V> v = ldv<V>(a.dm + (gr * N + mem[q]) * a.ld_dm + u);
+        if (a.mean) {
+            const int32_t* nbm = a.nbr + (gr * N + mem[q]) * a.deg;
+            int cm = 1;
+            for (int k = 0; k < a.deg; k++) cm += nbm[k] >= 0;
+            const float f = 1.0f / (float)cm;
+#pragma unroll
+            for (int e = 0; e < V; e++) v.v[e] = v.v[e] * f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; e++) g.v[e] += v.v[e];
+    }
+}
+
+// GRU cell backward with its gradient sources summed on the fly (gm_gru_cell_bwd), the counterpart of
+// k_lstm_cell_bwd / k_lstm_cell_bwd4. Thread (rl, uv) of a block of RL x H / V threads owns V consecutive units
+// of the rows r0 + rl, r0 + rl + RL, ... of the block's rows_per_block rows (V = 4: 16-byte loads and stores,
+// every ld and base 16-byte aligned). Rows and columns are indexed in 32 bits relative to the block's first row
+// (the host checks rows_per_block * ld < 2^31); only the dm gather reaches other blocks' rows. Bias partials:
+// the RL row lanes combined in LDS in a fixed order; max |dgates| per wave, then over the block's waves
+// (blockDim.x is a multiple of 64 for every accepted H).
+template <int V>
+__global__ __launch_bounds__(V == 4 ? 256 : 1024) void k_gru_cell_bwd(gm_gru_bwd_args a, unsigned* sc_slot,
+                                                                      unsigned* max_slot) {
+    constexpr int TPB = V == 4 ? 256 : 1024;
+    __shared__ __align__(16) float red[4][TPB * V];
+    __shared__ float wmx[TPB / 64];
+    const int H = a.hidden, HV = H / V, RL = blockDim.x / HV;
+    const int u = (threadIdx.x % HV) * V, rl = threadIdx.x / HV;
+    const long long r0 = (long long)blockIdx.x * a.rows_per_block;
+    const int nr = (int)min((long long)a.rows_per_block, (long long)a.m - r0);
+    const float* act = a.act + r0 * a.ld_act;
+    const float* hin = a.h + r0 * a.ld_h;
+    const float* dh0 = a.dh0 ? a.dh0 + r0 * a.ld_dh0 : nullptr;
+    const float* dh1 = a.dh1 ? a.dh1 + r0 * a.ld_dh1 : nullptr;
+    const float* dh2 = a.dh2 ? a.dh2 + r0 * a.ld_dh2 : nullptr;
+    const float* dhe = a.dh_ext ? a.dh_ext + r0 * a.ld_ext : nullptr;
+    float* dgb = a.dgates + r0 * a.ld_dg;
+    float* dhd = a.dh_dir ? a.dh_dir + r0 * a.ld_dhd : nullptr;
+    const int ld_act = (int)a.ld_act, ld_h = (int)a.ld_h, ld_dh0 = (int)a.ld_dh0, ld_dh1 = (int)a.ld_dh1,
+              ld_dh2 = (int)a.ld_dh2, ld_ext = (int)a.ld_ext, ld_dg = (int)a.ld_dg, ld_dhd = (int)a.ld_dhd;
+    Vec<V> p[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) p[k] = zerov<V>();
+    float mx = 0.f;
+    for (int i = rl; i < nr; i += RL) {
+        const float* ar = act + i * ld_act + u;
+        const Vec<V> rv = ldv<V>(ar), zv = ldv<V>(ar + H), nv = ldv<V>(ar + 2 * H), av = ldv<V>(ar + 3 * H);
+        const Vec<V> hv = ldv<V>(hin + i * ld_h + u);
+        Vec<V> g = zerov<V>();
+        auto add = [&g](const Vec<V>& s) {
+#pragma unroll
+            for (int e = 0; e < V; e++) g.v[e] += s.v[e];
+        };
+        if (dh0) add(ldv<V>(dh0 + i * ld_dh0 + u));
+        if (dh1) add(ldv<V>(dh1 + i * ld_dh1 + u));
+        if (dh2) add(ldv<V>(dh2 + i * ld_dh2 + u));
+        if (a.dm) gru_dm_add<V>(a, r0 + i, u, g);
+        if (dhe && (!a.ext_mask || !a.ext_mask[(r0 + i) / a.rows_per_sample])) add(ldv<V>(dhe + i * ld_ext + u));
+        Vec<V> o0, o1, o2, o3, od;
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            const float r = rv.v[e], z = zv.v[e], n = nv.v[e];
+            const float dan = g.v[e] * (1.f - z) * (1.f - n * n);
+            o0.v[e] = dan * av.v[e] * r * (1.f - r);
+            o1.v[e] = g.v[e] * (hv.v[e] - n) * z * (1.f - z);
+            o2.v[e] = dan;
+            o3.v[e] = dan * r;
+            od.v[e] = g.v[e] * z;
+            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(o0.v[e]), fabsf(o1.v[e])), fmaxf(fabsf(o2.v[e]), fabsf(o3.v[e]))));
+        }
+        float* dg = dgb + i * ld_dg + u;
+        stv<V>(dg, o0);
+        stv<V>(dg + H, o1);
+        stv<V>(dg + 2 * H, o2);
+        stv<V>(dg + 3 * H, o3);
+        if (dhd) stv<V>(dhd + i * ld_dhd + u, od);
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            p[0].v[e] += o0.v[e];
+            p[1].v[e] += o1.v[e];
+            p[2].v[e] += o2.v[e];
+            p[3].v[e] += o3.v[e];
+        }
+    }
+    if (a.bias_part) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) stv<V>(&red[k][threadIdx.x * V], p[k]);
+        __syncthreads();
+        if (rl == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                Vec<V> s = ldv<V>(&red[k][threadIdx.x * V]);
+                for (int l = 1; l < RL; l++) {
+                    const Vec<V> o = ldv<V>(&red[k][(l * HV + threadIdx.x) * V]);
+#pragma unroll
+                    for (int e = 0; e < V; e++) s.v[e] += o.v[e];
+                }
+                stv<V>(a.bias_part + (long long)blockIdx.x * 4 * H + k * H + u, s);
+            }
+        }
+    }
+    if (sc_slot || max_slot) {
+        mx = gm_wave_max(mx);
+        if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < (int)(blockDim.x >> 6); w++) mx = fmaxf(mx, wmx[w]);
+            if (sc_slot) gm_amax_publish(sc_slot, mx);
+            if (max_slot) gm_amax_publish(max_slot, mx);
+        }
+    }
 }
 }  // namespace
 
@@ -1867,6 +2035,71 @@ extern "C" int gm_gru_bwd(const float* gi, int64_t ldgi, const float* gh, int64_
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gm_fail(GM_ERR_HIP, std::string("gm_gru_bwd: ") + hipGetErrorString(e));
     return GM_OK;
+}
+
+extern "C" int gm_gru_cell_fwd(float* p, int64_t ldp, const float* h, int64_t ldh, int32_t m, int32_t H, float* h1,
+                               int64_t ldh1, void* stream) {
+    if (!p || !h || !h1 || m <= 0 || H <= 0 || ldp < 4 * (int64_t)H || ldh < H || ldh1 < H)
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_gru_cell_fwd: bad arguments (gate rows >= 4H)");
+    auto a16 = [](const void* q, long long ld) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0 && ld % 4 == 0; };
+    const bool vec = H % 4 == 0 && a16(p, ldp) && a16(h, ldh) && a16(h1, ldh1);
+    const long long n = (long long)m * (vec ? H / 4 : H);
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) {
+        GM_RAN("k_gru_cell_fwd<4>");
+        hipLaunchKernelGGL(k_gru_cell_fwd<4>, grid, blk, 0, st, p, (long long)ldp, h, (long long)ldh, m, H, h1,
+                           (long long)ldh1);
+    } else {
+        GM_RAN("k_gru_cell_fwd<1>");
+        hipLaunchKernelGGL(k_gru_cell_fwd<1>, grid, blk, 0, st, p, (long long)ldp, h, (long long)ldh, m, H, h1,
+                           (long long)ldh1);
+    }
+    return launched();
+}
+
+extern "C" int gm_gru_cell_bwd(const gm_gru_bwd_args* a, void* stream) {
+    if (!a || !a->act || !a->h || !a->dgates || a->m <= 0 || a->hidden <= 0 ||
+        (a->dm && (!a->nbr || a->n_nodes <= 0 || a->deg < 0 || a->deg > MAXDEG)) ||
+        (a->ext_mask && a->rows_per_sample <= 0) || (a->bias_part && a->rows_per_block <= 0))
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_gru_cell_bwd: bad arguments");
+    const int H = a->hidden;
+    if (!((H <= 256 && 256 % H == 0) || (H % 64 == 0 && H <= 1024)))
+        return gm_fail(GM_ERR_UNSUPPORTED, "gm_gru_cell_bwd: hidden must divide 256 or be a multiple of 64 up to 1024");
+    hipStream_t st = (hipStream_t)stream;
+    gm_gru_bwd_args b = *a;
+    if (b.rows_per_block <= 0) b.rows_per_block = 64;
+    // the kernels index a block's rows in 32 bits
+    long long ldmax = std::max((long long)b.ld_act, (long long)b.ld_dg);
+    for (long long ld : {(long long)b.ld_h, (long long)(b.dh0 ? b.ld_dh0 : 0), (long long)(b.dh1 ? b.ld_dh1 : 0),
+                         (long long)(b.dh2 ? b.ld_dh2 : 0), (long long)(b.dh_ext ? b.ld_ext : 0),
+                         (long long)(b.dh_dir ? b.ld_dhd : 0)})
+        ldmax = std::max(ldmax, ld);
+    if (b.ld_act < 4 * (int64_t)H || b.ld_dg < 4 * (int64_t)H || b.ld_h < H ||
+        (ldmax + 4 * (long long)H) * b.rows_per_block >= (1LL << 31))
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_gru_cell_bwd: row strides (>= 4H gate rows; rows_per_block * ld < 2^31)");
+    if (b.dg_scale && hipMemsetAsync(b.dg_scale, 0, sizeof(float), st) != hipSuccess)
+        return gm_fail(GM_ERR_HIP, "gm_gru_cell_bwd: memset");
+    const long long nb = ((long long)b.m + b.rows_per_block - 1) / b.rows_per_block;
+    auto a16 = [](const void* p, long long ld) { return !p || ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0); };
+    const bool vec = H % 4 == 0 && H / 4 <= 256 && ((256 / (H / 4)) * (H / 4)) % 64 == 0 && a16(b.act, b.ld_act) &&
+                     a16(b.h, b.ld_h) && a16(b.dh0, b.ld_dh0) && a16(b.dh1, b.ld_dh1) && a16(b.dh2, b.ld_dh2) &&
+                     a16(b.dm, b.ld_dm) && a16(b.dh_ext, b.ld_ext) && a16(b.dgates, b.ld_dg) &&
+                     a16(b.dh_dir, b.ld_dhd) && a16(b.bias_part, 4);
+    if (vec) {
+        const int rl4 = 256 / (H / 4);
+        GM_RAN("k_gru_cell_bwd<4>");
+        hipLaunchKernelGGL(k_gru_cell_bwd<4>, dim3((unsigned)nb), dim3(rl4 * (H / 4)), 0, st, b,
+                           reinterpret_cast<unsigned*>(b.dg_scale), reinterpret_cast<unsigned*>(b.dg_max));
+    } else {
+        const int RL = H >= 256 ? 1 : 256 / H;
+        GM_RAN("k_gru_cell_bwd<1>");
+        hipLaunchKernelGGL(k_gru_cell_bwd<1>, dim3((unsigned)nb), dim3(H * RL), 0, st, b,
+                           reinterpret_cast<unsigned*>(b.dg_scale), reinterpret_cast<unsigned*>(b.dg_max));
+    }
+    int rc = launched();
+    if (rc == GM_OK && b.dg_scale) rc = gm_absmax_finish(b.dg_scale, stream);
+    return rc;
 }
 
 // ---- per-step mean squared error of the SL unroll (src/sl.py:396-400: mse_loss(pred_all, targets_all) after

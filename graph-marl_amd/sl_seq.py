@@ -8,7 +8,11 @@ all of it with autograd. Here the NetMon part of the whole unroll is one autogra
 output is the readout of every node at every step, [L, B*N, 4H]; the heads and the loss stay in
 autograd and run once over all L steps' rows (sl.NetMonSL.forward_seq).
 
-Forward: the encoder MLP once (the observations are the same at every step), then per step the obs
+GRU cells (--netmon-rnn-type gru) run the same unroll with train_seq.py's GRU pieces: one GM_EPI_BIAS GEMM on
+the four-tile weight W4 + gm_gru_cell_fwd forward (state rows H wide, G = [r | z | n | a_nh] saved), and
+gm_gru_cell_bwd + one input-gradient GEMM on W4^T backward (_forward_gru / _backward_gru below).
+
+Forward (LSTM): the encoder MLP once (the observations are the same at every step), then per step the obs
 LSTM cell ([encoder output | h] as the GEMM's two sources, gate math in the epilogue) and K x
 (aggregate, update cell), the state carried in place (S[K, t-1] is step t's input state), the
 readout of every step.
@@ -32,10 +36,11 @@ from . import train_seq as TS
 
 def seq_bytes(netmon, rows, steps):
     """Device bytes the unroll keeps for its backward at M = rows node rows and L = steps: per cell and
-    step the [h | c] output (2H), the gate activations (4H) and their gradient (4H), plus the K
+    step the [h | c] output (2H; gru: h, H), the gate activations (4H) and their gradient (4H), plus the K
     aggregates (H), all fp32."""
     H, K = netmon.hidden_features, netmon.iterations
-    return 4 * steps * rows * ((K + 1) * 10 * H + K * H)
+    per_cell = 9 if netmon.rnn_type == "gru" else 10
+    return 4 * steps * rows * ((K + 1) * per_cell * H + K * H)
 
 
 def _device_room(dev):
@@ -44,7 +49,7 @@ def _device_room(dev):
 
 
 def seq_ok(netmon, rows=None, steps=None):
-    """The configurations this path covers: LSTM cells with carry-over, sum / mean aggregation,
+    """The configurations this path covers: LSTM or GRU cells with carry-over, sum / mean aggregation,
     neighbour readout without the global mean, leaky encoder layers with biases, split-f16 GEMMs;
     with rows / steps given, also that the unroll's saved tensors (seq_bytes) fit the device with a
     margin (otherwise the caller runs the per-step autograd path instead of failing with OOM)."""
@@ -52,7 +57,7 @@ def seq_ok(netmon, rows=None, steps=None):
         return False
     enc = list(netmon.encode.linear_layers)
     H = netmon.hidden_features
-    ok = (netmon.rnn_type == "lstm" and netmon.rnn_carryover and netmon.output_neighbor_hidden
+    ok = (TS.cell_ok(netmon) and netmon.rnn_carryover and netmon.output_neighbor_hidden
           and not netmon.output_global_hidden and netmon.iterations >= 1 and H % 32 == 0 and H <= 1024
           and len(enc) >= 1 and all(l.act == 1 and l.bias is not None for l in enc))
     if ok and rows is not None and steps is not None:
@@ -71,26 +76,11 @@ class _Plan:
     pass
 
 
-def _forward(p):
+def _encode(p, X, M, N, B, nbr):
+    """The encoder MLP once over the M node rows (sign bits and operand scales kept for the backward)."""
     netmon = p.netmon
-    X3d, nbr, Ls = p.x, p.nbr, p.steps
-    dev = X3d.device
-    B, N, F = X3d.shape
-    H = netmon.hidden_features
-    S2 = 2 * H
-    K = netmon.iterations
-    M = B * N
-    p.dims = (Ls, B, N, F, H, K, M)
-    mean = int(netmon.agg_mode == 1)
-    X = X3d.reshape(M, F)
-    if X.stride(0) % 4 or X.data_ptr() % 16:
-        Xp = torch.zeros(M, (F + 3) // 4 * 4, device=dev)
-        Xp[:, :F] = X
-        X = Xp
-    deg = nbr.shape[-1]
-    lib = L.lib()
-
-    # ---- encoder, once ----
+    dev = X.device
+    F = p.x.shape[2]
     enc = list(netmon.encode.linear_layers)
     p.enc_in, p.enc_out, p.enc_bits = [], [], []
     x, ldx, kx = X, X.stride(0), F
@@ -110,7 +100,194 @@ def _forward(p):
         p.enc_out.append(y)
         p.enc_bits.append(yb)
         x, ldx, kx = y, n, n
-    E = p.enc_out[-1]  # [M][H], every step's obs-cell input
+    return p.enc_out[-1]
+
+
+def _encoder_bwd(p, gEs, partE, grads):
+    """The encoder backward, once, on the gradient summed over the steps."""
+    Ls, B, N, F, H, K, M = p.dims
+    dev = gEs.device
+    enc = list(p.netmon.encode.linear_layers)
+    g = gEs.sum(0) if Ls > 1 else gEs[0]
+    sc = torch.empty(1, device=dev)
+    L.check(FU._setup().gm_absmax_scale(g.data_ptr(), g.numel(), sc.data_ptr(), L.stream_ptr()))
+    grads[enc[-1].bias] = partE.reshape(-1, H).sum(0)
+    for i in range(len(enc) - 1, -1, -1):
+        lin = enc[i]
+        xin, ldx, kin, sx = p.enc_in[i]
+        grads[lin.weight] = TS._wgrad(g, sc, xin, kin, sx)
+        if i > 0:
+            gn = torch.empty(M, kin, device=dev)
+            part = torch.empty((M + 127) // 128, kin, device=dev)
+            gmax = TS._zeros1(dev)
+            xb = p.enc_bits[i - 1]
+            TS._dgrad(g, lin.out_features, lin.out_features, sc, TS._lin_x3t(lin), M, kin, kin, xb, xb.stride(0), gn,
+                      kin, part=part, gmax=gmax)
+            grads[enc[i - 1].bias] = part.sum(0)
+            g, sc = gn, TS._finish(gmax)
+    return grads
+
+
+def _forward_gru(p):
+    """_forward for GRU cells: state rows [M][H]; per cell one W4 GEMM + gm_gru_cell_fwd (train_seq.gru_cell_fwd)."""
+    netmon = p.netmon
+    X3d, nbr, Ls = p.x, p.nbr, p.steps
+    dev = X3d.device
+    B, N, F = X3d.shape
+    H, K = netmon.hidden_features, netmon.iterations
+    M = B * N
+    p.dims = (Ls, B, N, F, H, K, M)
+    mean = int(netmon.agg_mode == 1)
+    X = X3d.reshape(M, F)
+    if X.stride(0) % 4 or X.data_ptr() % 16:
+        Xp = torch.zeros(M, (F + 3) // 4 * 4, device=dev)
+        Xp[:, :F] = X
+        X = Xp
+    deg = nbr.shape[-1]
+    lib = L.lib()
+    E = _encode(p, X, M, N, B, nbr)  # [M][H], every step's obs-cell input
+    S = torch.empty(K + 1, Ls, M, H, device=dev)  # cell outputs h: j = 0 obs, 1..K update
+    act = torch.empty(K + 1, Ls, M, 4 * H, device=dev)  # G = [r | z | n | a_nh]
+    agg = torch.empty(K, Ls, M, H, device=dev)
+    Z = torch.zeros(M, H, device=dev)  # the state starts at zero (src/sl.py:365)
+    s_obs, s_upd = TS._zeros1(dev), TS._zeros1(dev)
+    wo, wu = TS._gru_fwd(netmon.rnn_obs), TS._gru_fwd(netmon.rnn_update)
+    for t in range(Ls):
+        TS.gru_cell_fwd(E, Z if t == 0 else S[K, t - 1], H, *wo, M, H, s_obs, act[0, t], S[0, t], H)
+        for j in range(1, K + 1):
+            prev = S[j - 1, t]
+            L.check(lib.gm_mp_aggregate_rows(prev.data_ptr(), H, nbr.data_ptr(), B, N, deg, H, mean,
+                                             agg[j - 1, t].data_ptr(), H, L.stream_ptr()))
+            TS.gru_cell_fwd(agg[j - 1, t], prev, H, *wu, M, H, s_upd, act[j, t], S[j, t], H)
+    TS._finish(s_obs)
+    TS._finish(s_upd)
+    p.S, p.act, p.agg, p.Z, p.s_obs, p.s_upd = S, act, agg, Z, s_obs, s_upd
+    R = torch.empty(Ls * M, 4 * H, device=dev)
+    for t in range(Ls):
+        L.check(lib.gm_netmon_readout_ld(S[K, t].data_ptr(), H, S[K - 1, t].data_ptr(), H, nbr.data_ptr(), None, B, N,
+                                         N, deg, H, R[t * M:(t + 1) * M].data_ptr(), 4 * H, L.stream_ptr()))
+    netmon.state = S[K, Ls - 1].view(B, N, H)  # the state after the last step
+    return R.view(Ls, M, 4 * H)
+
+
+def _backward_gru(p, dR):
+    """_backward for GRU cells: gm_gru_cell_bwd + one input-gradient GEMM on W4^T per step and cell; a cell's h
+    gradient = the GEMM's h part + the direct part g z (two sources of the previous cell's call; added once for
+    the obs cell into step t-1's state gradient); W4's gradients mapped back to torch's layout."""
+    netmon = p.netmon
+    Ls, B, N, F, H, K, M = p.dims
+    dev = dR.device
+    nbr = p.nbr
+    deg = nbr.shape[-1]
+    lib = L.lib()
+    grads = {}
+    dR = dR.reshape(Ls * M, 4 * H).contiguous()
+    dhp = torch.empty(Ls * M, H, device=dev)
+    for t in range(Ls):
+        L.check(lib.gm_netmon_readout_bwd_sym(dR[t * M:(t + 1) * M].data_ptr(), 4 * H, nbr.data_ptr(), B, N, deg,
+                                              H, None, dhp[t * M:(t + 1) * M].data_ptr(), L.stream_ptr()))
+    S, act, Z = p.S, p.act, p.Z
+    dG = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
+    rpb_c = 64
+    bpart = torch.empty(K + 1, Ls, (M + rpb_c - 1) // rpb_c, 4 * H, device=dev)
+    gmax_obs, gmax_upd = TS._zeros1(dev), TS._zeros1(dev)
+    gEs = torch.empty(Ls, M, H, device=dev)  # the encoder output's gradient from each step's obs cell
+    partE = torch.empty(Ls, (M + 127) // 128, H, device=dev)
+    wt_obs, wt_upd = TS._gru_x3t(netmon.rnn_obs), TS._gru_x3t(netmon.rnn_update)
+    sc_cell = torch.empty(1, device=dev)
+    D = torch.empty(M, 2 * H, device=dev)
+    dhd_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    ext_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    Eb = p.enc_bits[-1]
+    mean = int(netmon.agg_mode == 1)
+    dh_ext = None
+    calls = 0
+    for t in range(Ls - 1, -1, -1):
+        dhd_next = None
+        for j in range(K, -1, -1):
+            a = L.GRUBwdArgs()
+            a.act, a.ld_act = act[j, t].data_ptr(), 4 * H
+            hin = (Z if t == 0 else S[K, t - 1]) if j == 0 else S[j - 1, t]
+            a.h, a.ld_h = hin.data_ptr(), H
+            if j == K:
+                a.dh0, a.ld_dh0 = dR[t * M:(t + 1) * M].data_ptr(), 4 * H  # dh_final: segment 0 of dR
+                if dh_ext is not None:  # step t+1's input-state gradient (no episode ends here)
+                    a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
+            else:
+                a.dh0, a.ld_dh0 = D.data_ptr() + 4 * H, 2 * H  # h part of the next cell's input gradient ...
+                a.dh2, a.ld_dh2 = dhd_next.data_ptr(), H       # ... and its direct part g z
+                a.dm, a.ld_dm = D.data_ptr(), 2 * H            # its aggregate part, transposed
+                a.nbr, a.n_nodes, a.deg, a.mean = nbr.data_ptr(), N, deg, mean
+            if j == K - 1:
+                a.dh1, a.ld_dh1 = dhp[t * M:(t + 1) * M].data_ptr(), H
+            a.m, a.hidden = M, H
+            a.dgates, a.ld_dg = dG[j, t].data_ptr(), 4 * H
+            dhd = None
+            if j > 0 or t > 0:  # the gradient w.r.t. the zero start state is not needed
+                dhd = dhd_buf[calls % 2]
+                a.dh_dir, a.ld_dhd = dhd.data_ptr(), H
+            calls += 1
+            a.bias_part, a.rows_per_block = bpart[j, t].data_ptr(), rpb_c
+            a.dg_scale = sc_cell.data_ptr()
+            a.dg_max = (gmax_obs if j == 0 else gmax_upd).data_ptr()
+            L.check(lib.gm_gru_cell_bwd(C.byref(a), L.stream_ptr()))
+            if j > 0:
+                TS._dgrad(dG[j, t], 4 * H, 4 * H, sc_cell, wt_upd, M, 2 * H, 2 * H, None, 0, D, 2 * H)
+            else:
+                ext = ext_buf[t % 2]
+                TS._dgrad(dG[0, t], 4 * H, 4 * H, sc_cell, wt_obs, M, 2 * H, H, Eb, Eb.stride(0), gEs[t], H, ext, H,
+                          part=partE[t])
+                if t > 0:
+                    ext.add_(dhd)
+                dh_ext = ext
+            dhd_next = dhd
+
+    # ---- cell weight / bias gradients: dW4's x and h halves, mapped back to torch's layout ----
+    sa_obs, sa_upd = TS._finish(gmax_obs), TS._finish(gmax_upd)
+    E = p.enc_out[-1]
+    # x half of the obs cell: every step's x is the same E (row map period M), as in the LSTM unroll
+    r = TS.MD._wgrad2(dG[0].reshape(Ls * M, 4 * H), [(E, H, p.s_obs, M, 0)], sa_obs) if Ls > 1 else None
+    if r is not None:
+        gx = r[0]
+    else:
+        gx = None
+        for t in range(Ls):
+            w_t = TS._wgrad(dG[0, t], sa_obs, E, H, p.s_obs)
+            gx = w_t if gx is None else gx.add_(w_t)
+    # h half: step 0's h is zero; step t's is S[K, t-1] (contiguous over t = 1..L-1)
+    if Ls > 1:
+        gh = TS._wgrad(dG[0, 1:].reshape(-1, 4 * H), sa_obs, S[K, :Ls - 1].reshape(-1, H), H, p.s_obs)
+    else:
+        gh = torch.zeros(4 * H, H, device=dev)
+    TS.gru_param_grads(netmon.rnn_obs, grads, gx, gh, bpart[0].reshape(-1, 4 * H).sum(0))
+    gx, gh = TS.MD._wgrad_pair(dG[1:].reshape(-1, 4 * H), p.agg.reshape(K * Ls * M, H), H,
+                               S[:K].reshape(K * Ls * M, H), H, sa_upd, p.s_upd, p.s_upd)
+    TS.gru_param_grads(netmon.rnn_update, grads, gx, gh, bpart[1:].reshape(-1, 4 * H).sum(0))
+    return _encoder_bwd(p, gEs, partE, grads)
+
+
+def _forward(p):
+    netmon = p.netmon
+    if netmon.rnn_type == "gru":
+        return _forward_gru(p)
+    X3d, nbr, Ls = p.x, p.nbr, p.steps
+    dev = X3d.device
+    B, N, F = X3d.shape
+    H = netmon.hidden_features
+    S2 = 2 * H
+    K = netmon.iterations
+    M = B * N
+    p.dims = (Ls, B, N, F, H, K, M)
+    mean = int(netmon.agg_mode == 1)
+    X = X3d.reshape(M, F)
+    if X.stride(0) % 4 or X.data_ptr() % 16:
+        Xp = torch.zeros(M, (F + 3) // 4 * 4, device=dev)
+        Xp[:, :F] = X
+        X = Xp
+    deg = nbr.shape[-1]
+    lib = L.lib()
+
+    E = _encode(p, X, M, N, B, nbr)  # [M][H], every step's obs-cell input
 
     # ---- LSTM cells, per step; the state starts at zero (src/sl.py:365) ----
     S = torch.empty(K + 1, Ls, M, S2, device=dev)  # cell outputs [h | c]: j = 0 obs, 1..K update
@@ -150,6 +327,8 @@ def _forward(p):
 
 def _backward(p, dR):
     netmon = p.netmon
+    if netmon.rnn_type == "gru":
+        return _backward_gru(p, dR)
     Ls, B, N, F, H, K, M = p.dims
     S2 = 2 * H
     dev = dR.device
@@ -263,26 +442,7 @@ def _backward(p, dR):
     grads[cell.bias_ih] = bg
     grads[cell.bias_hh] = bg.clone()
 
-    # ---- encoder, once, on the gradient summed over the steps ----
-    enc = list(netmon.encode.linear_layers)
-    g = gEs.sum(0) if Ls > 1 else gEs[0]
-    sc = torch.empty(1, device=dev)
-    L.check(FU._setup().gm_absmax_scale(g.data_ptr(), g.numel(), sc.data_ptr(), L.stream_ptr()))
-    grads[enc[-1].bias] = partE.reshape(-1, H).sum(0)
-    for i in range(len(enc) - 1, -1, -1):
-        lin = enc[i]
-        xin, ldx, kin, sx = p.enc_in[i]
-        grads[lin.weight] = TS._wgrad(g, sc, xin, kin, sx)
-        if i > 0:
-            gn = torch.empty(M, kin, device=dev)
-            part = torch.empty((M + 127) // 128, kin, device=dev)
-            gmax = TS._zeros1(dev)
-            xb = p.enc_bits[i - 1]
-            TS._dgrad(g, lin.out_features, lin.out_features, sc, TS._lin_x3t(lin), M, kin, kin, xb, xb.stride(0), gn,
-                      kin, part=part, gmax=gmax)
-            grads[enc[i - 1].bias] = part.sum(0)
-            g, sc = gn, TS._finish(gmax)
-    return grads
+    return _encoder_bwd(p, gEs, partE, grads)
 
 
 class _Fn(torch.autograd.Function):

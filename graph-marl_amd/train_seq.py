@@ -14,13 +14,20 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
     the gate math in its epilogue; backward: gm_lstm_cell_bwd, which sums every gradient source
     of the cell — readout, the next cell's input gradient, the transposed aggregate, the next
     step's state gradient masked at episode ends — and one input-gradient GEMM per cell);
+  * GRU cells (--netmon-rnn-type gru) take the same route on the four-tile weight W4 of
+    fused.pack_gru in natural row order: forward one GM_EPI_BIAS GEMM giving [a_r | a_z | a_nx |
+    a_nh], then gm_gru_cell_fwd (h', and G = [r | z | n | a_nh] saved in place); backward
+    gm_gru_cell_bwd and one input-gradient GEMM on W4^T giving [dx | dh_w]. The state rows are H
+    wide, and a cell's h gradient arrives in two parts (dh_w through W4 and the direct g z), which
+    the previous cell's call sums as two sources; the W4 weight gradient is mapped back to torch's
+    weight_ih / weight_hh / bias layout (gru_param_grads);
   * the leaky_relu derivative, the bias-gradient column sums and the gradient scales are fused
     into the kernels that produce the gradients (gm_gemm_x3_dgrad, gm_qhead_bwd,
-    gm_lstm_cell_bwd), so no activation gradient is re-read for them.
+    gm_lstm_cell_bwd / gm_gru_cell_bwd), so no activation gradient is re-read for them.
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(GRU / LN-LSTM cells, no carry-over, global readout, aux loss, DGN/DQNR/CommNet, GM_GEMM=f32).
+(LN-LSTM cells, no carry-over, global readout, aux loss, DGN/DQNR/CommNet, GM_GEMM=f32).
 """
 import ctypes as C
 from collections import namedtuple
@@ -36,13 +43,19 @@ SeqBatch = namedtuple("SeqBatch", ["obs", "obs_dim", "action", "reward", "done",
 """All L steps of B replay sequences, stacked: obs [L, B, A, odp] (rows padded to 16 bytes, first
 obs_dim columns valid), action [L, B, A] long, reward [L, B, A], done [L, B, A] bool, episode_done
 [L, B] bool, node_obs [L, B, N, F], nbr [L, B, N, deg] int32, agent_node [L, B, A] int32,
-node_state [B, N, 2H] (the NetMon state before step 0). next_fields(t, rows) -> (next_obs
+node_state [B, N, state_size] (the NetMon state before step 0: [h | c], gru: h). next_fields(t, rows) -> (next_obs
 [len, A, odp], next_node_obs [len, N, F], next_agent_node [len, A] int32) of step t for the
 sequences `rows` (None = all)."""
 
 
+def cell_ok(netmon):
+    """lstm, or gru at a hidden size gm_gru_cell_bwd takes (H <= 256 dividing 256, or a multiple of 64)."""
+    H = netmon.hidden_features
+    return netmon.rnn_type == "lstm" or (netmon.rnn_type == "gru" and (256 % H == 0 or H % 64 == 0))
+
+
 def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
-    """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM cells with
+    """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM or GRU cells with
     carry-over, sum / mean aggregation, neighbour readout, leaky MLPs, split-f16 GEMMs."""
     if netmon is None or aux_model is not None or att_coeff != 0 or L.GEMM_MODE != "x3":
         return False
@@ -52,7 +65,7 @@ def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
     enc = list(netmon.encode.linear_layers)
     dq = list(model.encoder.linear_layers)
     fc = model.q_net.fc
-    return (netmon.rnn_type == "lstm" and netmon.rnn_carryover and netmon.output_neighbor_hidden
+    return (cell_ok(netmon) and netmon.rnn_carryover and netmon.output_neighbor_hidden
             and not netmon.output_global_hidden and netmon.iterations >= 1 and H % 32 == 0 and H <= 1024
             and all(l.act == 1 for l in enc) and all(l.act == 1 for l in dq) and fc.act == 0
             and fc.out_features <= 4 and all(l.bias is not None for l in enc + dq + [fc])
@@ -132,6 +145,50 @@ def _lstm_fwd(cell):
     return wp, ldw, bp, x3
 
 
+def _gru_w4(cell):
+    """The four-tile weight of fused.pack_gru in natural row order: W4 [4H][2H] on A = [x | h] with row blocks r, z:
+    [W_i | W_h], n_x: [W_in | 0], n_h: [0 | W_hn], and its biases [b_ir + b_hr | b_iz + b_hz | b_in | b_hn]."""
+    H = cell.hidden_size
+    wi, wh, bi, bh = (t.detach() for t in (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh))
+    z = torch.zeros(H, H, device=wi.device)
+    w = torch.cat([torch.cat([wi[:2 * H], wh[:2 * H]], 1), torch.cat([wi[2 * H:], z], 1),
+                   torch.cat([z, wh[2 * H:]], 1)], 0)
+    return w, torch.cat([bi[:2 * H] + bh[:2 * H], bi[2 * H:], bh[2 * H:]])
+
+
+def _gru_fwd(cell):
+    """(b4, X3 of W4) for the cell's one GM_EPI_BIAS GEMM: P = [x | h] W4^T + b4 = [a_r | a_z | a_nx | a_nh]."""
+    def build():
+        w, b = _gru_w4(cell)
+        return b.contiguous(), _x3(w)
+    return _cache(cell).get("gru_fwd", FU._key(cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh), build)
+
+
+def _gru_x3t(cell):
+    """X3 of W4^T ([2H][4H], natural order) for d[x | h] = dgates @ W4."""
+    return _cache(cell).get("gru_t", FU._key(cell.weight_ih, cell.weight_hh),
+                            lambda: _x3(_gru_w4(cell)[0].t().contiguous()))
+
+
+def gru_cell_fwd(x, h, ldh, b4, x3, M, H, slot, G, out, ldo):
+    """One GRU cell: G [M][4H] = [x | h] W4^T + b4 (max |A| into slot), then gm_gru_cell_fwd: out = h' (strided
+    rows), G overwritten with [r | z | n | a_nh] for gm_gru_cell_bwd."""
+    FU.gemm(FU.dense(_ptr(x), H, H, amax=slot.data_ptr()), FU.dense(_ptr(h), ldh, H), None, 0, b4.data_ptr(), M,
+            4 * H, FU.GM_EPI_BIAS, _ptr(G), 4 * H, x3=x3)
+    L.check(L.lib().gm_gru_cell_fwd(_ptr(G), 4 * H, _ptr(h), ldh, M, H, _ptr(out), ldo, L.stream_ptr()))
+
+
+def gru_param_grads(cell, grads, gx, gh, bg):
+    """torch's GRUCell parameter layout from the W4 gradients: gx / gh [4H][H] = the x and h column halves of
+    dW4 (row blocks r, z, n_x, n_h; gx's n_h block and gh's n_x block belong to W4's zeros), bg [4H] the column
+    sums of the gate gradients (da_r, da_z, da_nx, da_nh)."""
+    H = cell.hidden_size
+    grads[cell.weight_ih] = gx[:3 * H]
+    grads[cell.weight_hh] = torch.cat([gh[:2 * H], gh[3 * H:]], 0)
+    grads[cell.bias_ih] = bg[:3 * H]
+    grads[cell.bias_hh] = torch.cat([bg[:2 * H], bg[3 * H:]])
+
+
 def _ptr(t):
     return t if isinstance(t, int) else t.data_ptr()
 
@@ -173,7 +230,8 @@ def _forward(p):
     N, F = sb.node_obs.shape[2], sb.node_obs.shape[3]
     od = sb.obs_dim
     H = netmon.hidden_features
-    S2 = 2 * H
+    gru = netmon.rnn_type == "gru"
+    S2 = H if gru else 2 * H  # state row: h, or [h | c]
     K = netmon.iterations
     M, Ma = B * N, B * A
     LM, LMa = Ls * M, Ls * Ma
@@ -211,34 +269,48 @@ def _forward(p):
         x, ldx, kx = y, n, n
     E = p.enc_out[-1]  # [LM][H], the obs cell's x
 
-    # ---- LSTM cells, per step ----
+    # ---- recurrent cells, per step ----
     S_in = torch.empty(Ls, M, S2, device=dev)
-    S = torch.empty(K + 1, Ls, M, S2, device=dev)  # cell outputs [h | c]: j = 0 obs, 1..K update
-    act = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
+    S = torch.empty(K + 1, Ls, M, S2, device=dev)  # cell outputs [h | c] (gru: h): j = 0 obs, 1..K update
+    act = torch.empty(K + 1, Ls, M, 4 * H, device=dev)  # gate activations (gru: G = [r | z | n | a_nh])
     agg = torch.empty(K, Ls, M, H, device=dev)
     s_obs, s_upd = _zeros1(dev), _zeros1(dev)
-    wo = _lstm_fwd(netmon.rnn_obs)
-    wu = _lstm_fwd(netmon.rnn_update)
     keep = (~sb.episode_done).to(torch.float32)  # [L, B]
     S_in[0].copy_(sb.node_state.reshape(M, S2))
     lib = L.lib()
-    for t in range(Ls):
-        if t > 0:  # the state carried from step t-1, zeroed at its episode end (src/main.py:858-866)
-            torch.mul(S[K, t - 1].view(B, N * S2), keep[t - 1].view(B, 1), out=S_in[t].view(B, N * S2))
-        src, sh = E[t * M:(t + 1) * M], S_in[t]
-        for j in range(K + 1):
-            wp, ldw, bp, x3 = wo if j == 0 else wu
-            if j == 0:
-                xa, hsrc = FU.dense(src.data_ptr(), H, H, amax=s_obs.data_ptr()), sh
-            else:
-                prev = S[j - 1, t]
-                L.check(lib.gm_mp_aggregate_rows(prev.data_ptr(), S2, nbr[t * B:(t + 1) * B].data_ptr(), B, N, deg, H,
-                                                 mean, agg[j - 1, t].data_ptr(), H, L.stream_ptr()))
-                xa, hsrc = FU.dense(agg[j - 1, t].data_ptr(), H, H, amax=s_upd.data_ptr()), prev
-            out = S[j, t]
-            FU.gemm(xa, FU.dense(hsrc.data_ptr(), S2, H), wp.data_ptr(), ldw, bp.data_ptr(), M, 4 * H, FU.GM_EPI_LSTM,
-                    out.data_ptr(), S2, out.data_ptr() + 4 * H, S2, hsrc.data_ptr() + 4 * H, S2, act[j, t].data_ptr(),
-                    x3=x3)
+    if gru:
+        wo, wu = _gru_fwd(netmon.rnn_obs), _gru_fwd(netmon.rnn_update)
+        for t in range(Ls):
+            if t > 0:
+                torch.mul(S[K, t - 1].view(B, N * H), keep[t - 1].view(B, 1), out=S_in[t].view(B, N * H))
+            for j in range(K + 1):
+                if j == 0:
+                    gru_cell_fwd(E[t * M:(t + 1) * M], S_in[t], H, *wo, M, H, s_obs, act[0, t], S[0, t], H)
+                else:
+                    prev = S[j - 1, t]
+                    L.check(lib.gm_mp_aggregate_rows(prev.data_ptr(), H, nbr[t * B:(t + 1) * B].data_ptr(), B, N, deg,
+                                                     H, mean, agg[j - 1, t].data_ptr(), H, L.stream_ptr()))
+                    gru_cell_fwd(agg[j - 1, t], prev, H, *wu, M, H, s_upd, act[j, t], S[j, t], H)
+    else:
+        wo = _lstm_fwd(netmon.rnn_obs)
+        wu = _lstm_fwd(netmon.rnn_update)
+        for t in range(Ls):
+            if t > 0:  # the state carried from step t-1, zeroed at its episode end (src/main.py:858-866)
+                torch.mul(S[K, t - 1].view(B, N * S2), keep[t - 1].view(B, 1), out=S_in[t].view(B, N * S2))
+            src, sh = E[t * M:(t + 1) * M], S_in[t]
+            for j in range(K + 1):
+                wp, ldw, bp, x3 = wo if j == 0 else wu
+                if j == 0:
+                    xa, hsrc = FU.dense(src.data_ptr(), H, H, amax=s_obs.data_ptr()), sh
+                else:
+                    prev = S[j - 1, t]
+                    L.check(lib.gm_mp_aggregate_rows(prev.data_ptr(), S2, nbr[t * B:(t + 1) * B].data_ptr(), B, N, deg,
+                                                     H, mean, agg[j - 1, t].data_ptr(), H, L.stream_ptr()))
+                    xa, hsrc = FU.dense(agg[j - 1, t].data_ptr(), H, H, amax=s_upd.data_ptr()), prev
+                out = S[j, t]
+                FU.gemm(xa, FU.dense(hsrc.data_ptr(), S2, H), wp.data_ptr(), ldw, bp.data_ptr(), M, 4 * H,
+                        FU.GM_EPI_LSTM, out.data_ptr(), S2, out.data_ptr() + 4 * H, S2, hsrc.data_ptr() + 4 * H, S2,
+                        act[j, t].data_ptr(), x3=x3)
     _finish(s_obs)
     _finish(s_upd)
     p.S_in, p.S, p.act, p.agg, p.s_obs, p.s_upd = S_in, S, act, agg, s_obs, s_upd
@@ -293,10 +365,93 @@ def _wgrad(g, sa, x, k, sb_):
     return MD._wgrad(g, x, k, sa, sb_)
 
 
+def _gru_cells_bwd(p, dhf, dhp, grads):
+    """GRU cells of _backward, per step and cell in reverse: gm_gru_cell_bwd (sums the cell's gradient sources,
+    writes the gate gradients dG and the direct h gradient g z), then one input-gradient GEMM on W4^T giving
+    D = [dx | dh_w]. The h input's gradient is dh_w + dh_dir: the previous cell's call takes the two as separate
+    sources; for the obs cell they are added once into the buffer that is step t-1's external state gradient.
+    Fills the cells' parameter gradients; returns (gE, partE, gmaxE) for the batched encoder backward."""
+    netmon = p.netmon
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
+    dev = dhf.device
+    LM = Ls * M
+    lib = L.lib()
+    dG = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
+    rpb_c = 64
+    nbc = (M + rpb_c - 1) // rpb_c
+    bpart = torch.empty(K + 1, Ls, nbc, 4 * H, device=dev)
+    gmax_obs, gmax_upd = _zeros1(dev), _zeros1(dev)
+    E = p.enc_out[-1]
+    Eb = p.enc_bits[-1]
+    gE = torch.empty(LM, H, device=dev)
+    partE = torch.empty(Ls, (M + 127) // 128, H, device=dev)
+    gmaxE = _zeros1(dev)
+    wt_obs, wt_upd = _gru_x3t(netmon.rnn_obs), _gru_x3t(netmon.rnn_update)
+    ep_done = p.seq.episode_done.to(torch.uint8).contiguous()  # [L, B]
+    sc_cell = torch.empty(1, device=dev)
+    D = torch.empty(M, 2 * H, device=dev)
+    dhd_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]  # dh_dir of the cell just processed
+    ext_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    dh_ext = None
+    calls = 0
+    mean = int(netmon.agg_mode == 1)
+    deg = p.nbr.shape[-1]
+    for t in range(Ls - 1, -1, -1):
+        nbr_t = p.nbr[t * B:(t + 1) * B]
+        dhd_next = None
+        for j in range(K, -1, -1):
+            a = L.GRUBwdArgs()
+            a.act, a.ld_act = p.act[j, t].data_ptr(), 4 * H
+            hin = p.S_in[t] if j == 0 else p.S[j - 1, t]
+            a.h, a.ld_h = hin.data_ptr(), H
+            if j == K:
+                a.dh0, a.ld_dh0 = dhf[t * M:(t + 1) * M].data_ptr(), H
+                if dh_ext is not None:  # step t+1's input-state gradient, zero where episode t ended
+                    a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
+                    a.ext_mask, a.rows_per_sample = ep_done[t].data_ptr(), N
+            else:
+                a.dh0, a.ld_dh0 = D.data_ptr() + 4 * H, 2 * H  # h part of the next cell's input gradient ...
+                a.dh2, a.ld_dh2 = dhd_next.data_ptr(), H       # ... and its direct part g z
+                a.dm, a.ld_dm = D.data_ptr(), 2 * H            # its aggregate part, transposed
+                a.nbr, a.n_nodes, a.deg, a.mean = nbr_t.data_ptr(), N, deg, mean
+            if j == K - 1:
+                a.dh1, a.ld_dh1 = dhp[t * M:(t + 1) * M].data_ptr(), H
+            a.m, a.hidden = M, H
+            a.dgates, a.ld_dg = dG[j, t].data_ptr(), 4 * H
+            dhd = None
+            if j > 0 or t > 0:  # the gradient w.r.t. the replayed start state is not needed
+                dhd = dhd_buf[calls % 2]
+                a.dh_dir, a.ld_dhd = dhd.data_ptr(), H
+            calls += 1
+            a.bias_part, a.rows_per_block = bpart[j, t].data_ptr(), rpb_c
+            a.dg_scale = sc_cell.data_ptr()
+            a.dg_max = (gmax_obs if j == 0 else gmax_upd).data_ptr()
+            L.check(lib.gm_gru_cell_bwd(C.byref(a), L.stream_ptr()))
+            if j > 0:
+                _dgrad(dG[j, t], 4 * H, 4 * H, sc_cell, wt_upd, M, 2 * H, 2 * H, None, 0, D, 2 * H)
+            else:
+                # [x | h] input gradient of the obs cell: x part through the encoder's last leaky_relu (bias
+                # partials and max for the batched encoder backward), h part + g z = the state gradient
+                ext = ext_buf[t % 2]
+                _dgrad(dG[0, t], 4 * H, 4 * H, sc_cell, wt_obs, M, 2 * H, H, Eb[t * M:(t + 1) * M], Eb.stride(0),
+                       gE[t * M:(t + 1) * M], H, ext, H, part=partE[t], gmax=gmaxE)
+                if t > 0:
+                    ext.add_(dhd)
+                dh_ext = ext
+            dhd_next = dhd
+    for j0, cell, gm_, sx, xs, hs in ((0, netmon.rnn_obs, gmax_obs, p.s_obs, E, p.S_in.reshape(LM, H)),
+                                      (1, netmon.rnn_update, gmax_upd, p.s_upd, p.agg.reshape(K * LM, H),
+                                       p.S[:K].reshape(K * LM, H))):
+        n = 1 if j0 == 0 else K
+        gx, gh = MD._wgrad_pair(dG[j0:j0 + n].reshape(-1, 4 * H), xs, H, hs, H, _finish(gm_), sx, sx)
+        gru_param_grads(cell, grads, gx, gh, bpart[j0:j0 + n].reshape(-1, 4 * H).sum(0))
+    return gE, partE, gmaxE
+
+
 def _backward(p, dq):
     netmon, dqn = p.netmon, p.dqn
     Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
-    S2 = 2 * H
+    S2 = 2 * H  # (lstm branch)
     dev = dq.device
     LM, LMa = Ls * M, Ls * Ma
     lib = L.lib()
@@ -351,85 +506,88 @@ def _backward(p, dq):
     L.check(lib.gm_netmon_readout_bwd(dR.data_ptr(), 4 * H, p.nbr.data_ptr(), p.an.data_ptr(), Ls * B, N, A,
                                       p.nbr.shape[-1], H, dhf.data_ptr(), dhp.data_ptr(), L.stream_ptr()))
 
-    # ---- LSTM cells, per step, in reverse ----
-    dG = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
-    rpb_c = 64
-    nbc = (M + rpb_c - 1) // rpb_c
-    bpart = torch.empty(K + 1, Ls, nbc, 4 * H, device=dev)
-    gmax_obs, gmax_upd = _zeros1(dev), _zeros1(dev)
-    E = p.enc_out[-1]
-    gE = torch.empty(LM, H, device=dev)
-    nbe = (M + 127) // 128
-    partE = torch.empty(Ls, nbe, H, device=dev)
-    gmaxE = _zeros1(dev)
-    wt_obs, wt_upd = _lstm_x3t(netmon.rnn_obs), _lstm_x3t(netmon.rnn_update)
-    ep_done = p.seq.episode_done.to(torch.uint8).contiguous()  # [L, B]
-    dh_ext = dc_ext = None
-    sc_cell = torch.empty(1, device=dev)
-    D = torch.empty(M, S2, device=dev)
-    dh0_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
-    # every cell's dc source is the dc output of the cell processed just before it (the next cell
-    # of the step, or step t+1's obs cell): two buffers in turn
-    dc_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
-    calls = 0
-    mean = int(netmon.agg_mode == 1)
-    deg = p.nbr.shape[-1]
-    for t in range(Ls - 1, -1, -1):
-        nbr_t = p.nbr[t * B:(t + 1) * B]
-        dc_next = None
-        have_D = False
-        for j in range(K, -1, -1):
-            a = L.LSTMBwdArgs()
-            a.act, a.ld_act = p.act[j, t].data_ptr(), 4 * H
-            cin = p.S_in[t] if j == 0 else p.S[j - 1, t]
-            a.c_in, a.ld_cin = cin.data_ptr() + 4 * H, S2
-            a.c_out, a.ld_cout = p.S[j, t].data_ptr() + 4 * H, S2
-            if j == K:
-                a.dh0, a.ld_dh0 = dhf[t * M:(t + 1) * M].data_ptr(), H
-            else:
-                a.dh0, a.ld_dh0 = D.data_ptr() + 4 * H, S2  # h part of the next cell's input gradient
-                a.dm, a.ld_dm = D.data_ptr(), S2            # its aggregate part, transposed
-                a.nbr, a.n_nodes, a.deg, a.mean = nbr_t.data_ptr(), N, deg, mean
-            if j == K - 1:
-                a.dh1, a.ld_dh1 = dhp[t * M:(t + 1) * M].data_ptr(), H
-            if j == K and dh_ext is not None:  # step t+1's input-state gradient, zero where episode t ended
-                a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
-                a.dc_ext, a.ld_dcext = dc_ext.data_ptr(), H
-                a.ext_mask, a.rows_per_sample = ep_done[t].data_ptr(), N
-            if dc_next is not None:
-                a.dc, a.ld_dc = dc_next.data_ptr(), H
-            a.m, a.hidden = M, H
-            a.dgates, a.ld_dg = dG[j, t].data_ptr(), 4 * H
-            dco = None
-            if j > 0 or t > 0:  # the gradient w.r.t. the replayed start state is not needed
-                dco = dc_buf[calls % 2]
-                a.dc_out, a.ld_dco = dco.data_ptr(), H
-            calls += 1
-            a.bias_part, a.rows_per_block = bpart[j, t].data_ptr(), rpb_c
-            a.dg_scale = sc_cell.data_ptr()
-            a.dg_max = (gmax_obs if j == 0 else gmax_upd).data_ptr()
-            L.check(lib.gm_lstm_cell_bwd(C.byref(a), L.stream_ptr()))
-            if j > 0:
-                _dgrad(dG[j, t], 4 * H, 4 * H, sc_cell, wt_upd, M, S2, S2, None, 0, D, S2)
-            else:
-                # [x | h] input gradient of the obs cell: x part through the encoder's last leaky_relu
-                # (bias partials and max for the batched encoder backward), h part = the state gradient
-                dh0 = dh0_buf[t % 2]
-                Eb = p.enc_bits[-1]
-                _dgrad(dG[0, t], 4 * H, 4 * H, sc_cell, wt_obs, M, S2, H, Eb[t * M:(t + 1) * M], Eb.stride(0),
-                       gE[t * M:(t + 1) * M], H, dh0, H, part=partE[t], gmax=gmaxE)
-                dh_ext, dc_ext = dh0, dco
-            dc_next = dco
-    # LSTM weight / bias gradients over all steps (and update iterations)
-    for j0, cell, gm_, sx, xs, hs in ((0, netmon.rnn_obs, gmax_obs, p.s_obs, E, p.S_in.reshape(LM, S2)),
-                                      (1, netmon.rnn_update, gmax_upd, p.s_upd, p.agg.reshape(K * LM, H),
-                                       p.S[:K].reshape(K * LM, S2))):
-        gs = dG[j0:j0 + (1 if j0 == 0 else K)].reshape(-1, 4 * H)
-        sa = _finish(gm_)
-        grads[cell.weight_ih], grads[cell.weight_hh] = MD._wgrad_pair(gs, xs, H, hs, H, sa, sx, sx)
-        bg = bpart[j0:j0 + (1 if j0 == 0 else K)].reshape(-1, 4 * H).sum(0)
-        grads[cell.bias_ih] = bg
-        grads[cell.bias_hh] = bg.clone()
+    # ---- recurrent cells, per step, in reverse ----
+    if netmon.rnn_type == "gru":
+        gE, partE, gmaxE = _gru_cells_bwd(p, dhf, dhp, grads)
+    else:
+        dG = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
+        rpb_c = 64
+        nbc = (M + rpb_c - 1) // rpb_c
+        bpart = torch.empty(K + 1, Ls, nbc, 4 * H, device=dev)
+        gmax_obs, gmax_upd = _zeros1(dev), _zeros1(dev)
+        E = p.enc_out[-1]
+        gE = torch.empty(LM, H, device=dev)
+        nbe = (M + 127) // 128
+        partE = torch.empty(Ls, nbe, H, device=dev)
+        gmaxE = _zeros1(dev)
+        wt_obs, wt_upd = _lstm_x3t(netmon.rnn_obs), _lstm_x3t(netmon.rnn_update)
+        ep_done = p.seq.episode_done.to(torch.uint8).contiguous()  # [L, B]
+        dh_ext = dc_ext = None
+        sc_cell = torch.empty(1, device=dev)
+        D = torch.empty(M, S2, device=dev)
+        dh0_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+        # every cell's dc source is the dc output of the cell processed just before it (the next cell
+        # of the step, or step t+1's obs cell): two buffers in turn
+        dc_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+        calls = 0
+        mean = int(netmon.agg_mode == 1)
+        deg = p.nbr.shape[-1]
+        for t in range(Ls - 1, -1, -1):
+            nbr_t = p.nbr[t * B:(t + 1) * B]
+            dc_next = None
+            have_D = False
+            for j in range(K, -1, -1):
+                a = L.LSTMBwdArgs()
+                a.act, a.ld_act = p.act[j, t].data_ptr(), 4 * H
+                cin = p.S_in[t] if j == 0 else p.S[j - 1, t]
+                a.c_in, a.ld_cin = cin.data_ptr() + 4 * H, S2
+                a.c_out, a.ld_cout = p.S[j, t].data_ptr() + 4 * H, S2
+                if j == K:
+                    a.dh0, a.ld_dh0 = dhf[t * M:(t + 1) * M].data_ptr(), H
+                else:
+                    a.dh0, a.ld_dh0 = D.data_ptr() + 4 * H, S2  # h part of the next cell's input gradient
+                    a.dm, a.ld_dm = D.data_ptr(), S2            # its aggregate part, transposed
+                    a.nbr, a.n_nodes, a.deg, a.mean = nbr_t.data_ptr(), N, deg, mean
+                if j == K - 1:
+                    a.dh1, a.ld_dh1 = dhp[t * M:(t + 1) * M].data_ptr(), H
+                if j == K and dh_ext is not None:  # step t+1's input-state gradient, zero where episode t ended
+                    a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
+                    a.dc_ext, a.ld_dcext = dc_ext.data_ptr(), H
+                    a.ext_mask, a.rows_per_sample = ep_done[t].data_ptr(), N
+                if dc_next is not None:
+                    a.dc, a.ld_dc = dc_next.data_ptr(), H
+                a.m, a.hidden = M, H
+                a.dgates, a.ld_dg = dG[j, t].data_ptr(), 4 * H
+                dco = None
+                if j > 0 or t > 0:  # the gradient w.r.t. the replayed start state is not needed
+                    dco = dc_buf[calls % 2]
+                    a.dc_out, a.ld_dco = dco.data_ptr(), H
+                calls += 1
+                a.bias_part, a.rows_per_block = bpart[j, t].data_ptr(), rpb_c
+                a.dg_scale = sc_cell.data_ptr()
+                a.dg_max = (gmax_obs if j == 0 else gmax_upd).data_ptr()
+                L.check(lib.gm_lstm_cell_bwd(C.byref(a), L.stream_ptr()))
+                if j > 0:
+                    _dgrad(dG[j, t], 4 * H, 4 * H, sc_cell, wt_upd, M, S2, S2, None, 0, D, S2)
+                else:
+                    # [x | h] input gradient of the obs cell: x part through the encoder's last leaky_relu
+                    # (bias partials and max for the batched encoder backward), h part = the state gradient
+                    dh0 = dh0_buf[t % 2]
+                    Eb = p.enc_bits[-1]
+                    _dgrad(dG[0, t], 4 * H, 4 * H, sc_cell, wt_obs, M, S2, H, Eb[t * M:(t + 1) * M], Eb.stride(0),
+                           gE[t * M:(t + 1) * M], H, dh0, H, part=partE[t], gmax=gmaxE)
+                    dh_ext, dc_ext = dh0, dco
+                dc_next = dco
+        # LSTM weight / bias gradients over all steps (and update iterations)
+        for j0, cell, gm_, sx, xs, hs in ((0, netmon.rnn_obs, gmax_obs, p.s_obs, E, p.S_in.reshape(LM, S2)),
+                                          (1, netmon.rnn_update, gmax_upd, p.s_upd, p.agg.reshape(K * LM, H),
+                                           p.S[:K].reshape(K * LM, S2))):
+            gs = dG[j0:j0 + (1 if j0 == 0 else K)].reshape(-1, 4 * H)
+            sa = _finish(gm_)
+            grads[cell.weight_ih], grads[cell.weight_hh] = MD._wgrad_pair(gs, xs, H, hs, H, sa, sx, sx)
+            bg = bpart[j0:j0 + (1 if j0 == 0 else K)].reshape(-1, 4 * H).sum(0)
+            grads[cell.bias_ih] = bg
+            grads[cell.bias_hh] = bg.clone()
 
     # ---- NetMon encoder over all steps ----
     enc = list(netmon.encode.linear_layers)
@@ -489,12 +647,12 @@ def _target_max(p, model_tar, gamma_unused=None):
         for t in torch.unique(done_rows[:, 0]).tolist():
             r = done_rows[done_rows[:, 0] == t, 1].to(dev)
             no, nno, nan_ = sb.next_fields(t, r)
-            st = p.S[K, t].view(B, N, 2 * H)[r]
+            st = p.S[K, t].view(B, N, netmon.state_size)[r]
             nb = sb.nbr[t][r]
             out[t, r] = _fused_next_q(netmon, model_tar, no[..., :od], nno, nb, nan_, st).max(dim=2)[0]
     no, nno, nan_ = sb.next_fields(Ls - 1, None)
     out[-1] = _fused_next_q(netmon, model_tar, no[..., :od], nno, sb.nbr[-1], nan_,
-                            p.S[K, Ls - 1].view(B, N, 2 * H)).max(dim=2)[0]
+                            p.S[K, Ls - 1].view(B, N, netmon.state_size)).max(dim=2)[0]
     return out
 
 

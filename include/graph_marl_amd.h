@@ -342,6 +342,47 @@ typedef struct {
     float* dg_max;
 } gm_lstm_bwd_args;
 int gm_lstm_cell_bwd(const gm_lstm_bwd_args* a, void* stream);
+/* GRU cell of the sequence-batched training path (nn.GRUCell, src/model.py:387-393). The cell runs on
+ * A = [x | h] and the four-tile weight W4 [4H][2H] with row blocks r, z: [W_i | W_h], n_x: [W_in | 0],
+ * n_h: [0 | W_hn] and biases b_ir + b_hr, b_iz + b_hz, b_in, b_hn, so that one GM_EPI_BIAS gm_gemm_x3 gives
+ * the pre-activations P = [a_r | a_z | a_nx | a_nh] ([m][4H], row stride ldp >= 4H).
+ * gm_gru_cell_fwd: per row and unit r = sigmoid(a_r), z = sigmoid(a_z), n = tanh(a_nx + r a_nh),
+ * h1 = (1 - z) n + z h (h, h1 strided rows; the arithmetic of gm_gru_pointwise, bit for bit); P is
+ * overwritten in place with G = [r | z | n | a_nh], the activations gm_gru_cell_bwd reads. Any H. */
+int gm_gru_cell_fwd(float* p, int64_t ldp, const float* h, int64_t ldh, int32_t m, int32_t hidden, float* h1,
+                    int64_t ldh1, void* stream);
+/* gm_gru_cell_bwd (backward of torch autograd through the cell): per row r and unit u, with the saved
+ * G = act (r, z, n, a_nh) and the cell's input state h:
+ *   g     = dh0 + dh1 + dh2 + sum_{n in {r} U nbr(r)} dm[n] s(n) + (ext_mask[r / rows_per_sample] ? 0 : dh_ext)
+ *   dn    = g (1 - z)      dz = g (h - n)       dh_dir = g z
+ *   da_n  = dn (1 - n^2)   da_nx = da_n         da_nh = da_n r      dr = da_n a_nh
+ *   da_r  = dr r (1 - r)   da_z = dz z (1 - z)
+ * (every source nullable; dm = the input gradient of the aggregate input of the next cell, s(n) = 1 or
+ * 1 / |{n} U nbr(n)| for mean, -1 entries skipped: gm_lstm_cell_bwd's sources, plus dh2 because the next
+ * cell's h gradient arrives in two parts, through W4 and directly); writes dgates = [da_r | da_z | da_nx |
+ * da_nh] ([m][ld_dg], columns >= 4H untouched), dh_dir [m][H] (nullable), per-block column sums of dgates
+ * to bias_part [ceil(m / rows_per_block)][4H] (nullable), max |dgates| to dg_scale as a power-of-two scale
+ * (gm_absmax_scale semantics, nullable) and as float bits into dg_max (nullable, accumulated by atomicMax).
+ * H <= 256 with 256 % H == 0, or H % 64 == 0 with H <= 1024; any other H: GM_ERR_UNSUPPORTED, nothing
+ * launched. rows_per_block (default 64) times the largest row stride must stay below 2^31. */
+typedef struct {
+    const float* act; int64_t ld_act;
+    const float* h; int64_t ld_h;
+    const float* dh0; int64_t ld_dh0;
+    const float* dh1; int64_t ld_dh1;
+    const float* dh2; int64_t ld_dh2;
+    const float* dm; int64_t ld_dm;
+    const int32_t* nbr; int32_t n_nodes, deg, mean;
+    const float* dh_ext; int64_t ld_ext;
+    const uint8_t* ext_mask; int32_t rows_per_sample;
+    int32_t m, hidden;
+    float* dgates; int64_t ld_dg;
+    float* dh_dir; int64_t ld_dhd;
+    float* bias_part; int32_t rows_per_block;
+    float* dg_scale;
+    float* dg_max;
+} gm_gru_bwd_args;
+int gm_gru_cell_bwd(const gm_gru_bwd_args* a, void* stream);
 /* Q head + last hidden layer backward (Q_Net.fc after a leaky_relu MLP layer, src/model.py:119-125,
  * 187-203): g[r][c] = (sum_a dq[r][a] wq[a][c]) * (act && y[r][c] <= 0 ? 0.01 : 1) for the layer
  * output y; per block of rows_per_block rows: part_b[blk][c] = sum g (the layer's bias gradient),
