@@ -35,7 +35,7 @@ EXPORTS = [
     "gm_gemm_x3_dgrad", "gm_lstm_cell_bwd", "gm_qhead_bwd", "gm_netmon_readout_ld", "gm_routing_node_encoder_bits", "gm_gather_records",
     "gm_lnlstm_fwd", "gm_lnlstm_bwd", "gm_gru_pointwise", "gm_gru_bwd", "gm_act_bwd", "gm_build_info",
     "gm_act_fwd", "gm_act_bwd_z", "gm_obs_from_gemm", "gm_encoder_x3", "gm_step_mse_blocks", "gm_step_mse",
-    "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd",
+    "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
@@ -107,6 +107,25 @@ class GRUBwdArgs(C.Structure):
         ("m", C.c_int32), ("hidden", C.c_int32), ("dgates", C.c_void_p), ("ld_dg", C.c_int64),
         ("dh_dir", C.c_void_p), ("ld_dhd", C.c_int64), ("bias_part", C.c_void_p), ("rows_per_block", C.c_int32),
         ("dg_scale", C.c_void_p), ("dg_max", C.c_void_p),
+    ]
+
+
+class LNLSTMBwdArgs(C.Structure):
+    """gm_lnlstm_cell_bwd_args (include/graph_marl_amd.h)."""
+    _fields_ = [
+        ("gi", C.c_void_p), ("ld_gi", C.c_int64), ("gh", C.c_void_p), ("ld_gh", C.c_int64),
+        ("c_in", C.c_void_p), ("ld_cin", C.c_int64), ("ln_in_w", C.c_void_p), ("ln_in_b", C.c_void_p),
+        ("ln_hid_w", C.c_void_p), ("ln_hid_b", C.c_void_p), ("bias", C.c_void_p), ("ln_cell_w", C.c_void_p),
+        ("ln_cell_b", C.c_void_p), ("eps", C.c_float), ("stats", C.c_void_p),
+        ("dh0", C.c_void_p), ("ld_dh0", C.c_int64), ("dh1", C.c_void_p), ("ld_dh1", C.c_int64),
+        ("dm", C.c_void_p), ("ld_dm", C.c_int64),
+        ("nbr", C.c_void_p), ("n_nodes", C.c_int32), ("deg", C.c_int32), ("mean", C.c_int32),
+        ("dh_ext", C.c_void_p), ("ld_ext", C.c_int64), ("dc_ext", C.c_void_p), ("ld_dcext", C.c_int64),
+        ("ext_mask", C.c_void_p), ("rows_per_sample", C.c_int32), ("dc", C.c_void_p), ("ld_dc", C.c_int64),
+        ("m", C.c_int32), ("hidden", C.c_int32), ("dgi", C.c_void_p), ("ld_dgi", C.c_int64),
+        ("dgh", C.c_void_p), ("ld_dgh", C.c_int64), ("dc_out", C.c_void_p), ("ld_dco", C.c_int64),
+        ("part", C.c_void_p), ("rows_per_wave", C.c_int32), ("dgi_scale", C.c_void_p), ("dgi_max", C.c_void_p),
+        ("dgh_scale", C.c_void_p), ("dgh_max", C.c_void_p),
     ]
 
 
@@ -194,6 +213,7 @@ def lib():
         "gm_netmon_readout_bwd_sym": [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp],
         "gm_gru_cell_fwd": [vp, i64, vp, i64, i32, i32, vp, i64, vp],
         "gm_gru_cell_bwd": [C.POINTER(GRUBwdArgs), vp],
+        "gm_lnlstm_cell_bwd": [C.POINTER(LNLSTMBwdArgs), vp],
     }
     for name, at in newer.items():
         if hasattr(L, name) or not os.environ.get("GM_LIB"):

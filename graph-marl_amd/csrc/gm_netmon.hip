@@ -1590,6 +1590,136 @@ __global__ __launch_bounds__(256) void k_lnlstm_pw(const float* __restrict__ Gi,
 //   LN_in^T / LN_hid^T: dni = dG w_i, d gi = r_i (dni - mean dni - n_i mean(dni n_i)) (same for h)
 // Parameter gradients are accumulated per wave in registers and written as one partial row per wave:
 // part[wave][14H] = [d w_i (4H) | d w_h (4H) | d bias (4H; also d b_i and d b_h) | d w_c (H) | d b_c (H)].
+
+// the per-wave parameter-gradient accumulators of the LayerNorm-LSTM backward kernels
+template <int UPL>
+struct LnLstmAcc {
+    float wi[UPL][4], wh[UPL][4], b[UPL][4], wc[UPL], bc[UPL];
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int q = 0; q < UPL; q++) {
+            wc[q] = bc[q] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) wi[q][k] = wh[q][k] = b[q][k] = 0.f;
+        }
+    }
+    __device__ __forceinline__ void store(float* pr, int H, int lane) const {
+#pragma unroll
+        for (int q = 0; q < UPL; q++) {
+            const int u = lane + 64 * q;
+            if (u >= H) continue;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                pr[k * H + u] = wi[q][k];
+                pr[4 * H + k * H + u] = wh[q][k];
+                pr[8 * H + k * H + u] = b[q][k];
+            }
+            pr[12 * H + u] = wc[q];
+            pr[13 * H + u] = bc[q];
+        }
+    }
+};
+
+// One row of the LayerNorm-LSTM backward, in ONE operation order for both kernels that run it (k_lnlstm_bwd and
+// k_lnlstm_cell_bwd give the same bits on the same row gradients): gh1 / gc1 = the row's total gradient of h' and
+// c' for this lane's units (zero beyond H), dgi / dgh the row's output rows, dco (nullable) the row's d c; the
+// parameter gradients go into acc, max |d gi| / |d gh| into mxi / mxh when AMAX.
+template <int UPL, bool AMAX>
+__device__ __forceinline__ void lnlstm_row_bwd(const float* __restrict__ gi, const float* __restrict__ gh,
+                                               const float* __restrict__ cin, const LnLstmP& p,
+                                               const float* __restrict__ st, int H, int lane, const float (&gh1)[UPL],
+                                               const float (&gc1)[UPL], float* __restrict__ dgi,
+                                               float* __restrict__ dgh, float* __restrict__ dco, LnLstmAcc<UPL>& acc,
+                                               float& mxi, float& mxh) {
+    // every product and sum rounded on its own, so the result does not depend on what the surrounding kernel
+    // lets the compiler contract into an fma
+#pragma clang fp contract(off)
+    const float inv4h = 1.0f / (float)(4 * H), invh = 1.0f / (float)H;
+    const float mi = st[0], ri = st[1], mh = st[2], rh = st[3], mc = st[4], rc = st[5];
+    float ni[UPL][4], nh[UPL][4], act[UPL][4], cx[UPL], nc[UPL], dcy[UPL], dO[UPL];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < UPL; q++) {
+        const int u = lane + 64 * q;
+        cx[q] = nc[q] = dcy[q] = dO[q] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) ni[q][k] = nh[q][k] = act[q][k] = 0.f;
+        if (u >= H) continue;
+        float g[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int col = k * H + u;
+            ni[q][k] = (gi[col] - mi) * ri;
+            nh[q][k] = (gh[col] - mh) * rh;
+            g[k] = (ni[q][k] * p.gi_w[col] + p.gi_b[col]) + (nh[q][k] * p.gh_w[col] + p.gh_b[col]) + p.bias[col];
+        }
+        act[q][0] = sig_f(g[0]);
+        act[q][1] = sig_f(g[1]);
+        act[q][2] = tanh_f(g[2]);
+        act[q][3] = sig_f(g[3]);
+        cx[q] = cin[u];
+        const float cp = act[q][1] * cx[q] + act[q][0] * act[q][2];
+        nc[q] = (cp - mc) * rc;
+        const float cy = nc[q] * p.lc_w[u] + p.lc_b[u];
+        const float th = tanh_f(cy);
+        dcy[q] = gc1[q] + gh1[q] * act[q][3] * (1.f - th * th);
+        dO[q] = gh1[q] * th;
+        acc.wc[q] += dcy[q] * nc[q];
+        acc.bc[q] += dcy[q];
+        const float dn = dcy[q] * p.lc_w[u];
+        s1 += dn;
+        s2 += dn * nc[q];
+    }
+    const float m1 = wsum(s1) * invh, m2 = wsum(s2) * invh;
+    float dG[UPL][4];
+    float ti1 = 0.f, ti2 = 0.f, th1 = 0.f, th2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < UPL; q++) {
+        const int u = lane + 64 * q;
+#pragma unroll
+        for (int k = 0; k < 4; k++) dG[q][k] = 0.f;
+        if (u >= H) continue;
+        const float du = rc * (dcy[q] * p.lc_w[u] - m1 - nc[q] * m2);
+        const float i = act[q][0], f = act[q][1], gg = act[q][2], o = act[q][3];
+        if (dco) dco[u] = du * f;
+        dG[q][0] = du * gg * i * (1.f - i);
+        dG[q][1] = du * cx[q] * f * (1.f - f);
+        dG[q][2] = du * i * (1.f - gg * gg);
+        dG[q][3] = dO[q] * o * (1.f - o);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int col = k * H + u;
+            acc.b[q][k] += dG[q][k];
+            acc.wi[q][k] += dG[q][k] * ni[q][k];
+            acc.wh[q][k] += dG[q][k] * nh[q][k];
+            const float a = dG[q][k] * p.gi_w[col], b = dG[q][k] * p.gh_w[col];
+            ti1 += a;
+            ti2 += a * ni[q][k];
+            th1 += b;
+            th2 += b * nh[q][k];
+        }
+    }
+    const float mi1 = wsum(ti1) * inv4h, mi2 = wsum(ti2) * inv4h;
+    const float mh1 = wsum(th1) * inv4h, mh2 = wsum(th2) * inv4h;
+#pragma unroll
+    for (int q = 0; q < UPL; q++) {
+        const int u = lane + 64 * q;
+        if (u >= H) continue;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int col = k * H + u;
+            const float oi = ri * (dG[q][k] * p.gi_w[col] - mi1 - ni[q][k] * mi2);
+            const float oh = rh * (dG[q][k] * p.gh_w[col] - mh1 - nh[q][k] * mh2);
+            dgi[col] = oi;
+            dgh[col] = oh;
+            if (AMAX) {
+                mxi = fmaxf(mxi, fabsf(oi));
+                mxh = fmaxf(mxh, fabsf(oh));
+            }
+        }
+    }
+}
+
 template <int UPL>
 __global__ __launch_bounds__(256) void k_lnlstm_bwd(const float* __restrict__ Gi, long long ldgi,
                                                     const float* __restrict__ Gh, long long ldgh,
@@ -1604,110 +1734,100 @@ __global__ __launch_bounds__(256) void k_lnlstm_bwd(const float* __restrict__ Gi
     const long long r0 = wave * rpw;
     if (r0 >= M) return;  // wave-uniform
     const long long r1 = r0 + rpw < M ? r0 + rpw : M;
-    float pwi[UPL][4], pwh[UPL][4], pb[UPL][4], pwc[UPL], pbc[UPL];
-#pragma unroll
-    for (int q = 0; q < UPL; q++) {
-        pwc[q] = pbc[q] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; k++) pwi[q][k] = pwh[q][k] = pb[q][k] = 0.f;
-    }
-    const float inv4h = 1.0f / (float)(4 * H), invh = 1.0f / (float)H;
+    LnLstmAcc<UPL> acc;
+    acc.zero();
+    float mxi = 0.f, mxh = 0.f;
     for (long long row = r0; row < r1; row++) {
-        const float mi = stats[row * 8 + 0], ri = stats[row * 8 + 1], mh = stats[row * 8 + 2],
-                    rh = stats[row * 8 + 3], mc = stats[row * 8 + 4], rc = stats[row * 8 + 5];
-        const float* gi = Gi + row * ldgi;
-        const float* gh = Gh + row * ldgh;
-        float ni[UPL][4], nh[UPL][4], act[UPL][4], cx[UPL], nc[UPL], dcy[UPL], dO[UPL];
-        float s1 = 0.f, s2 = 0.f;
+        float gh1[UPL], gc1[UPL];
 #pragma unroll
         for (int q = 0; q < UPL; q++) {
             const int u = lane + 64 * q;
-            cx[q] = nc[q] = dcy[q] = dO[q] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) ni[q][k] = nh[q][k] = act[q][k] = 0.f;
-            if (u >= H) continue;
-            float g[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int col = k * H + u;
-                ni[q][k] = (gi[col] - mi) * ri;
-                nh[q][k] = (gh[col] - mh) * rh;
-                g[k] = (ni[q][k] * p.gi_w[col] + p.gi_b[col]) + (nh[q][k] * p.gh_w[col] + p.gh_b[col]) + p.bias[col];
-            }
-            act[q][0] = sig_f(g[0]);
-            act[q][1] = sig_f(g[1]);
-            act[q][2] = tanh_f(g[2]);
-            act[q][3] = sig_f(g[3]);
-            cx[q] = c_in[row * ldc + u];
-            const float cp = act[q][1] * cx[q] + act[q][0] * act[q][2];
-            nc[q] = (cp - mc) * rc;
-            const float cy = nc[q] * p.lc_w[u] + p.lc_b[u];
-            const float th = tanh_f(cy);
-            const float gh1 = dh1 ? dh1[row * lddh + u] : 0.f;
-            dcy[q] = (dc1 ? dc1[row * lddc + u] : 0.f) + gh1 * act[q][3] * (1.f - th * th);
-            dO[q] = gh1 * th;
-            pwc[q] += dcy[q] * nc[q];
-            pbc[q] += dcy[q];
-            const float dn = dcy[q] * p.lc_w[u];
-            s1 += dn;
-            s2 += dn * nc[q];
+            const bool ok = u < H;
+            gh1[q] = ok && dh1 ? dh1[row * lddh + u] : 0.f;
+            gc1[q] = ok && dc1 ? dc1[row * lddc + u] : 0.f;
         }
-        const float m1 = wsum(s1) * invh, m2 = wsum(s2) * invh;
-        float dG[UPL][4];
-        float ti1 = 0.f, ti2 = 0.f, th1 = 0.f, th2 = 0.f;
-#pragma unroll
-        for (int q = 0; q < UPL; q++) {
-            const int u = lane + 64 * q;
-#pragma unroll
-            for (int k = 0; k < 4; k++) dG[q][k] = 0.f;
-            if (u >= H) continue;
-            const float du = rc * (dcy[q] * p.lc_w[u] - m1 - nc[q] * m2);
-            const float i = act[q][0], f = act[q][1], gg = act[q][2], o = act[q][3];
-            dc[row * lddco + u] = du * f;
-            dG[q][0] = du * gg * i * (1.f - i);
-            dG[q][1] = du * cx[q] * f * (1.f - f);
-            dG[q][2] = du * i * (1.f - gg * gg);
-            dG[q][3] = dO[q] * o * (1.f - o);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int col = k * H + u;
-                pb[q][k] += dG[q][k];
-                pwi[q][k] += dG[q][k] * ni[q][k];
-                pwh[q][k] += dG[q][k] * nh[q][k];
-                const float a = dG[q][k] * p.gi_w[col], b = dG[q][k] * p.gh_w[col];
-                ti1 += a;
-                ti2 += a * ni[q][k];
-                th1 += b;
-                th2 += b * nh[q][k];
-            }
-        }
-        const float mi1 = wsum(ti1) * inv4h, mi2 = wsum(ti2) * inv4h;
-        const float mh1 = wsum(th1) * inv4h, mh2 = wsum(th2) * inv4h;
-#pragma unroll
-        for (int q = 0; q < UPL; q++) {
-            const int u = lane + 64 * q;
-            if (u >= H) continue;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int col = k * H + u;
-                dgi[row * lddgi + col] = ri * (dG[q][k] * p.gi_w[col] - mi1 - ni[q][k] * mi2);
-                dgh[row * lddgh + col] = rh * (dG[q][k] * p.gh_w[col] - mh1 - nh[q][k] * mh2);
-            }
-        }
+        lnlstm_row_bwd<UPL, false>(Gi + row * ldgi, Gh + row * ldgh, c_in + row * ldc, p, stats + row * 8, H, lane,
+                                   gh1, gc1, dgi + row * lddgi, dgh + row * lddgh, dc + row * lddco, acc, mxi, mxh);
     }
-    float* pr = part + wave * 14LL * H;
+    acc.store(part + wave * 14LL * H, H, lane);
+}
+
+// LayerNorm-LSTM cell backward of the sequence-batched training path (gm_lnlstm_cell_bwd): k_lnlstm_bwd's wave
+// and unit ownership and its row math (lnlstm_row_bwd), with the row's gradient of h' and c' summed on the fly
+// from every source of the cell as k_lstm_cell_bwd sums them (dh0, dh1, the transposed (I + A) aggregate of dm
+// in ascending member order, dh_ext / dc_ext unless the row's sample is masked, dc); each lane gathers its own
+// units of at most deg + 1 dm rows in 64-wide runs. max |d gi| and max |d gh| are published once per wave.
+template <int UPL>
+__global__ __launch_bounds__(256) void k_lnlstm_cell_bwd(gm_lnlstm_cell_bwd_args a, LnLstmP p, unsigned* sci,
+                                                         unsigned* sch) {
+    const int lane = threadIdx.x & 63;
+    const int H = a.hidden, rpw = a.rows_per_wave;
+    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long r0 = wave * rpw;
+    if (r0 >= a.m) return;  // wave-uniform
+    const long long r1 = r0 + rpw < a.m ? r0 + rpw : a.m;
+    LnLstmAcc<UPL> acc;
+    acc.zero();
+    float mxi = 0.f, mxh = 0.f;
+    for (long long row = r0; row < r1; row++) {
+        float gh1[UPL], gc1[UPL];
 #pragma unroll
-    for (int q = 0; q < UPL; q++) {
-        const int u = lane + 64 * q;
-        if (u >= H) continue;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            pr[k * H + u] = pwi[q][k];
-            pr[4 * H + k * H + u] = pwh[q][k];
-            pr[8 * H + k * H + u] = pb[q][k];
+        for (int q = 0; q < UPL; q++) gh1[q] = gc1[q] = 0.f;
+        int mem[MAXDEG + 1];
+        float ms[MAXDEG + 1];
+        int cnt = 0;
+        long long g0 = 0;  // first row of the row's graph
+        if (a.dm) {        // transpose of the (I + A) aggregate: members of the row's node, ascending id
+            const int N = a.n_nodes;
+            const long long g = row / N;
+            g0 = g * N;
+            cnt = members(a.nbr + row * a.deg, a.deg, (int)(row - g0), mem);
+            for (int e = 0; e < cnt; e++) {
+                ms[e] = 1.0f;
+                if (a.mean) {
+                    const int32_t* nbm = a.nbr + (g0 + mem[e]) * a.deg;
+                    int cm = 1;
+                    for (int k = 0; k < a.deg; k++) cm += nbm[k] >= 0;
+                    ms[e] = 1.0f / (float)cm;
+                }
+            }
         }
-        pr[12 * H + u] = pwc[q];
-        pr[13 * H + u] = pbc[q];
+        const bool ext = !a.ext_mask || !a.ext_mask[row / a.rows_per_sample];
+#pragma unroll
+        for (int q = 0; q < UPL; q++) {
+            const int u = lane + 64 * q;
+            if (u >= H) continue;
+            float dh = 0.f, dcn = 0.f;
+            if (a.dh0) dh += a.dh0[row * a.ld_dh0 + u];
+            if (a.dh1) dh += a.dh1[row * a.ld_dh1 + u];
+            for (int e = 0; e < cnt; e++) {
+                float v = a.dm[(g0 + mem[e]) * a.ld_dm + u];
+                if (a.mean) v = v * ms[e];
+                dh += v;
+            }
+            if (a.dc) dcn += a.dc[row * a.ld_dc + u];
+            if (ext) {
+                if (a.dh_ext) dh += a.dh_ext[row * a.ld_ext + u];
+                if (a.dc_ext) dcn += a.dc_ext[row * a.ld_dcext + u];
+            }
+            gh1[q] = dh;
+            gc1[q] = dcn;
+        }
+        lnlstm_row_bwd<UPL, true>(a.gi + row * a.ld_gi, a.gh + row * a.ld_gh, a.c_in + row * a.ld_cin, p,
+                                  a.stats + row * 8, H, lane, gh1, gc1, a.dgi + row * a.ld_dgi,
+                                  a.dgh + row * a.ld_dgh, a.dc_out ? a.dc_out + row * a.ld_dco : nullptr, acc, mxi,
+                                  mxh);
+    }
+    if (a.part) acc.store(a.part + wave * 14LL * H, H, lane);
+    if (sci || a.dgi_max || sch || a.dgh_max) {
+        mxi = gm_wave_max(mxi);
+        mxh = gm_wave_max(mxh);
+        if (lane == 0) {
+            if (sci) gm_amax_publish(sci, mxi);
+            if (a.dgi_max) gm_amax_publish(reinterpret_cast<unsigned*>(a.dgi_max), mxi);
+            if (sch) gm_amax_publish(sch, mxh);
+            if (a.dgh_max) gm_amax_publish(reinterpret_cast<unsigned*>(a.dgh_max), mxh);
+        }
     }
 }
 
@@ -2007,6 +2127,47 @@ extern "C" int gm_lnlstm_bwd(const float* gi, int64_t ldgi, const float* gh, int
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gm_fail(GM_ERR_HIP, std::string("gm_lnlstm_bwd: ") + hipGetErrorString(e));
     return GM_OK;
+}
+
+extern "C" int gm_lnlstm_cell_bwd(const gm_lnlstm_cell_bwd_args* a, void* stream) {
+    if (!a || !a->gi || !a->gh || !a->c_in || !a->stats || !a->dgi || !a->dgh || !a->ln_in_w || !a->ln_in_b ||
+        !a->ln_hid_w || !a->ln_hid_b || !a->bias || !a->ln_cell_w || !a->ln_cell_b || a->m <= 0 || a->hidden <= 0 ||
+        !(a->eps >= 0.f) || (a->dm && (!a->nbr || a->n_nodes <= 0 || a->deg < 0 || a->deg > MAXDEG)) ||
+        (a->ext_mask && a->rows_per_sample <= 0) || a->rows_per_wave < 0)
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_lnlstm_cell_bwd: bad arguments");
+    const int H = a->hidden;
+    if (H > 512) return gm_fail(GM_ERR_UNSUPPORTED, "gm_lnlstm_cell_bwd: hidden must be at most 512");
+    const int64_t H4 = 4 * (int64_t)H;
+    if (a->ld_gi < H4 || a->ld_gh < H4 || a->ld_dgi < H4 || a->ld_dgh < H4 || a->ld_cin < H ||
+        (a->dh0 && a->ld_dh0 < H) || (a->dh1 && a->ld_dh1 < H) || (a->dm && a->ld_dm < H) ||
+        (a->dh_ext && a->ld_ext < H) || (a->dc_ext && a->ld_dcext < H) || (a->dc && a->ld_dc < H) ||
+        (a->dc_out && a->ld_dco < H))
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_lnlstm_cell_bwd: row strides (gate rows >= 4H, state rows >= H)");
+    hipStream_t st = (hipStream_t)stream;
+    gm_lnlstm_cell_bwd_args b = *a;
+    if (b.rows_per_wave <= 0) b.rows_per_wave = 8;
+    if (!b.ext_mask) b.rows_per_sample = 1;
+    for (float* s : {b.dgi_scale, b.dgh_scale})
+        if (s && hipMemsetAsync(s, 0, sizeof(float), st) != hipSuccess)
+            return gm_fail(GM_ERR_HIP, "gm_lnlstm_cell_bwd: memset");
+    LnLstmP p{b.ln_in_w, b.ln_in_b, b.ln_hid_w, b.ln_hid_b, b.bias, b.ln_cell_w, b.ln_cell_b};
+    const long long waves = ((long long)b.m + b.rows_per_wave - 1) / b.rows_per_wave;
+    const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
+    unsigned* sci = reinterpret_cast<unsigned*>(b.dgi_scale);
+    unsigned* sch = reinterpret_cast<unsigned*>(b.dgh_scale);
+    GM_RAN("k_lnlstm_cell_bwd");
+    if (H <= 64)
+        hipLaunchKernelGGL(k_lnlstm_cell_bwd<1>, grid, blk, 0, st, b, p, sci, sch);
+    else if (H <= 128)
+        hipLaunchKernelGGL(k_lnlstm_cell_bwd<2>, grid, blk, 0, st, b, p, sci, sch);
+    else if (H <= 256)
+        hipLaunchKernelGGL(k_lnlstm_cell_bwd<4>, grid, blk, 0, st, b, p, sci, sch);
+    else
+        hipLaunchKernelGGL(k_lnlstm_cell_bwd<8>, grid, blk, 0, st, b, p, sci, sch);
+    int rc = launched();
+    if (rc == GM_OK && b.dgi_scale) rc = gm_absmax_finish(b.dgi_scale, stream);
+    if (rc == GM_OK && b.dgh_scale) rc = gm_absmax_finish(b.dgh_scale, stream);
+    return rc;
 }
 
 extern "C" int gm_gru_pointwise(const float* gi, int64_t ldgi, const float* gh, int64_t ldgh, const float* h,

@@ -239,6 +239,12 @@ def _step_mse_fits(pred, tgt):
             and pred.data_ptr() % 16 == 0 and tgt.data_ptr() % 16 == 0)
 
 
+# cell types train_step sends to the sequence-batched unroll. sl_seq.py also covers lnlstm, but at config 5's shape
+# it measured 174.7 ms against 188.1 ms per iteration (7 %, inside the box-to-box spread: a tie), so lnlstm stays
+# on the per-step autograd path (tools/gru_seq_bench.py adds it here to time the unroll)
+SEQ_RNN_TYPES = ("lstm", "gru")
+
+
 def train_step(args, model, optim, data, batch_idx):
     """One iteration of src/sl.py:360-424."""
     model.netmon.state = None
@@ -246,6 +252,7 @@ def train_step(args, model, optim, data, batch_idx):
     tgt_all, tgt, labels = data.targets_all[batch_idx], data.targets[batch_idx], data.labels[batch_idx]
     steps = max(args.sequence_length, 1)
     if (WITH_REGRESSION_ALL and not WITH_CLASSIFICATION and not WITH_REGRESSION
+            and model.netmon.rnn_type in SEQ_RNN_TYPES
             and SQ.seq_ok(model.netmon, rows=obs.shape[0] * obs.shape[1], steps=steps)
             and not getattr(args, "sl_autograd", False)):
         # sequence-batched NetMon (sl_seq.py): the mean of the per-step MSEs over all steps' rows at once

@@ -12,6 +12,12 @@ GRU cells (--netmon-rnn-type gru) run the same unroll with train_seq.py's GRU pi
 the four-tile weight W4 + gm_gru_cell_fwd forward (state rows H wide, G = [r | z | n | a_nh] saved), and
 gm_gru_cell_bwd + one input-gradient GEMM on W4^T backward (_forward_gru / _backward_gru below).
 
+LayerNorm-LSTM cells (--netmon-rnn-type lnlstm) run it with train_seq.py's LN-LSTM pieces (_forward_lnl /
+_backward_lnl): two no-bias GEMMs per cell into saved raw products + gm_lnlstm_fwd, and gm_lnlstm_cell_bwd + the
+input-gradient GEMMs backward. The obs cell's x is the same encoder output at every step and its LayerNorm sees
+x W_ih^T alone, so that product is computed once and its gradient is summed over the steps before one W_ih weight
+gradient and the one encoder backward. (sl.py itself keeps lnlstm on the autograd path: DESIGN §5a.)
+
 Forward (LSTM): the encoder MLP once (the observations are the same at every step), then per step the obs
 LSTM cell ([encoder output | h] as the GEMM's two sources, gate math in the epilogue) and K x
 (aggregate, update cell), the state carried in place (S[K, t-1] is step t's input state), the
@@ -37,8 +43,15 @@ from . import train_seq as TS
 def seq_bytes(netmon, rows, steps):
     """Device bytes the unroll keeps for its backward at M = rows node rows and L = steps: per cell and
     step the [h | c] output (2H; gru: h, H), the gate activations (4H) and their gradient (4H), plus the K
-    aggregates (H), all fp32."""
+    aggregates (H), all fp32; lnlstm: the tensors _forward_lnl / _backward_lnl keep (kept_lnl)."""
     H, K = netmon.hidden_features, netmon.iterations
+    if netmon.rnn_type == "lnlstm":
+        # per cell and step the [h | c] row (2H) and the 8 statistics; the raw gate products and their gradients:
+        # the obs cell's gi once (its x is the same at every step) with its gradient summed over the steps (one
+        # step's buffer + the sum), its gh (4H) and d gh (4H) per step, the update cells' 8H + 8H per step; the
+        # K aggregates (H)
+        per_step = (K + 1) * (2 * H + 8) + 8 * H + K * 16 * H + K * H
+        return 4 * rows * (steps * per_step + 12 * H)
     per_cell = 9 if netmon.rnn_type == "gru" else 10
     return 4 * steps * rows * ((K + 1) * per_cell * H + K * H)
 
@@ -49,7 +62,7 @@ def _device_room(dev):
 
 
 def seq_ok(netmon, rows=None, steps=None):
-    """The configurations this path covers: LSTM or GRU cells with carry-over, sum / mean aggregation,
+    """The configurations this path covers: LSTM, GRU or LayerNorm-LSTM cells with carry-over, sum / mean aggregation,
     neighbour readout without the global mean, leaky encoder layers with biases, split-f16 GEMMs;
     with rows / steps given, also that the unroll's saved tensors (seq_bytes) fit the device with a
     margin (otherwise the caller runs the per-step autograd path instead of failing with OOM)."""
@@ -266,10 +279,182 @@ def _backward_gru(p, dR):
     return _encoder_bwd(p, gEs, partE, grads)
 
 
+def kept_lnl(p):
+    """The tensors the LayerNorm-LSTM unroll keeps between its forward and the end of its backward (what seq_bytes
+    counts for lnlstm)."""
+    return [p.S, p.stats, p.agg, p.gi_obs, p.gh_obs, p.g_upd] + list(getattr(p, "bwd_kept", []))
+
+
+def _forward_lnl(p):
+    """_forward for LayerNorm-LSTM cells: state rows [h | c]; per cell two no-bias GEMMs (x W_ih^T, h W_hh^T) into
+    saved raw products + gm_lnlstm_fwd. The obs cell's x is the encoder output at every step and its LayerNorm
+    sees x W_ih^T alone: gi_obs is computed once."""
+    netmon = p.netmon
+    X3d, nbr, Ls = p.x, p.nbr, p.steps
+    dev = X3d.device
+    B, N, F = X3d.shape
+    H, K = netmon.hidden_features, netmon.iterations
+    S2 = 2 * H
+    M = B * N
+    p.dims = (Ls, B, N, F, H, K, M)
+    mean = int(netmon.agg_mode == 1)
+    X = X3d.reshape(M, F)
+    if X.stride(0) % 4 or X.data_ptr() % 16:
+        Xp = torch.zeros(M, (F + 3) // 4 * 4, device=dev)
+        Xp[:, :F] = X
+        X = Xp
+    deg = nbr.shape[-1]
+    lib = L.lib()
+    E = _encode(p, X, M, N, B, nbr)  # [M][H], every step's obs-cell input
+    co, cu = netmon.rnn_obs, netmon.rnn_update
+    S = torch.empty(K + 1, Ls, M, S2, device=dev)  # cell outputs [h | c]: j = 0 obs, 1..K update
+    stats = torch.empty(K + 1, Ls, M, 8, device=dev)
+    agg = torch.empty(K, Ls, M, H, device=dev)
+    gi_obs = torch.empty(M, 4 * H, device=dev)
+    gh_obs = torch.empty(Ls, M, 4 * H, device=dev)
+    g_upd = torch.empty(K, Ls, M, 8 * H, device=dev)
+    Z = torch.zeros(M, S2, device=dev)  # the state starts at zero (src/sl.py:365)
+    s_obs, s_upd, sh_obs, sh_upd = (TS._zeros1(dev) for _ in range(4))
+    TS.lnl_gemm(E, H, co, False, M, H, s_obs, gi_obs, 4 * H)
+    for t in range(Ls):
+        sh = Z if t == 0 else S[K, t - 1]
+        TS.lnl_gemm(sh, S2, co, True, M, H, sh_obs, gh_obs[t], 4 * H)
+        TS.lnl_cell_fwd(co, gi_obs, 4 * H, gh_obs[t], 4 * H, sh, S[0, t], M, H, stats[0, t])
+        for j in range(1, K + 1):
+            prev, G = S[j - 1, t], g_upd[j - 1, t]
+            L.check(lib.gm_mp_aggregate_rows(prev.data_ptr(), S2, nbr.data_ptr(), B, N, deg, H, mean,
+                                             agg[j - 1, t].data_ptr(), H, L.stream_ptr()))
+            TS.lnl_gemm(agg[j - 1, t], H, cu, False, M, H, s_upd, G, 8 * H)
+            TS.lnl_gemm(prev, S2, cu, True, M, H, sh_upd, G.data_ptr() + 16 * H, 8 * H)
+            TS.lnl_cell_fwd(cu, G, 8 * H, G.data_ptr() + 16 * H, 8 * H, prev, S[j, t], M, H, stats[j, t])
+    for sl in (s_obs, s_upd, sh_obs, sh_upd):
+        TS._finish(sl)
+    p.S, p.stats, p.agg, p.Z, p.gi_obs, p.gh_obs, p.g_upd = S, stats, agg, Z, gi_obs, gh_obs, g_upd
+    p.s_obs, p.s_upd, p.sh_obs, p.sh_upd = s_obs, s_upd, sh_obs, sh_upd
+    R = torch.empty(Ls * M, 4 * H, device=dev)
+    for t in range(Ls):
+        L.check(lib.gm_netmon_readout_ld(S[K, t].data_ptr(), S2, S[K - 1, t].data_ptr(), S2, nbr.data_ptr(), None, B,
+                                         N, N, deg, H, R[t * M:(t + 1) * M].data_ptr(), 4 * H, L.stream_ptr()))
+    netmon.set_state_hc(S[K, Ls - 1, :, :H], S[K, Ls - 1, :, H:], B, N)  # the state after the last step
+    return R.view(Ls, M, 4 * H)
+
+
+def _backward_lnl(p, dR):
+    """_backward for LayerNorm-LSTM cells: gm_lnlstm_cell_bwd per step and cell in reverse, then dgh @ W_hh (h
+    part) and, for the update cell, dgi @ W_ih (the previous cell's transposed-aggregate source). The obs cell's
+    dgi is summed over the steps (its x is the same E at every step): one W_ih weight gradient and one input
+    gradient through the encoder's last leaky mask on the sum, before the one encoder backward."""
+    netmon = p.netmon
+    Ls, B, N, F, H, K, M = p.dims
+    S2 = 2 * H
+    dev = dR.device
+    nbr = p.nbr
+    deg = nbr.shape[-1]
+    lib = L.lib()
+    grads = {}
+    dR = dR.reshape(Ls * M, 4 * H).contiguous()
+    dhp = torch.empty(Ls * M, H, device=dev)
+    for t in range(Ls):
+        L.check(lib.gm_netmon_readout_bwd_sym(dR[t * M:(t + 1) * M].data_ptr(), 4 * H, nbr.data_ptr(), B, N, deg,
+                                              H, None, dhp[t * M:(t + 1) * M].data_ptr(), L.stream_ptr()))
+    S, Z = p.S, p.Z
+    co, cu = netmon.rnn_obs, netmon.rnn_update
+    dgi_t = torch.empty(M, 4 * H, device=dev)      # the obs cell's dgi of one step ...
+    dgi_sum = torch.empty(M, 4 * H, device=dev)    # ... and its sum over the steps
+    dgh_obs = torch.empty(Ls, M, 4 * H, device=dev)
+    dgi_upd = torch.empty(K, Ls, M, 4 * H, device=dev)
+    dgh_upd = torch.empty(K, Ls, M, 4 * H, device=dev)
+    p.bwd_kept = [dgi_t, dgi_sum, dgh_obs, dgi_upd, dgh_upd]
+    nw = (M + TS.LNL_RPW - 1) // TS.LNL_RPW
+    part = torch.empty(nw, 14 * H, device=dev)  # one call's per-wave partials, summed into psum right after it
+    psum = torch.empty(K + 1, Ls, 14 * H, device=dev)
+    mx = {k: TS._zeros1(dev) for k in ("gh_obs", "gi_upd", "gh_upd")}
+    sc_i, sc_h = torch.empty(1, device=dev), torch.empty(1, device=dev)
+    (wti_obs, wth_obs), (wti_upd, wth_upd) = TS._lnl_x3t(co), TS._lnl_x3t(cu)
+    Dx, Dh = torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)
+    dh0_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    dc_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    mean = int(netmon.agg_mode == 1)
+    dh_ext = dc_ext = None
+    calls = 0
+    for t in range(Ls - 1, -1, -1):
+        dc_next = None
+        for j in range(K, -1, -1):
+            if j == 0:
+                a = TS.lnl_bwd_args(co, p.gi_obs, 4 * H, p.gh_obs[t], 4 * H, Z if t == 0 else S[K, t - 1],
+                                    p.stats[0, t], M, H)
+                dgi, dgh = dgi_sum if t == Ls - 1 else dgi_t, dgh_obs[t]
+            else:
+                G = p.g_upd[j - 1, t]
+                a = TS.lnl_bwd_args(cu, G, 8 * H, G.data_ptr() + 16 * H, 8 * H, S[j - 1, t], p.stats[j, t], M, H)
+                dgi, dgh = dgi_upd[j - 1, t], dgh_upd[j - 1, t]
+            if j == K:
+                a.dh0, a.ld_dh0 = dR[t * M:(t + 1) * M].data_ptr(), 4 * H  # dh_final: segment 0 of dR
+            else:
+                a.dh0, a.ld_dh0 = Dh.data_ptr(), H  # h part of the next cell's input gradient
+                a.dm, a.ld_dm = Dx.data_ptr(), H    # its aggregate part, transposed
+                a.nbr, a.n_nodes, a.deg, a.mean = nbr.data_ptr(), N, deg, mean
+            if j == K - 1:
+                a.dh1, a.ld_dh1 = dhp[t * M:(t + 1) * M].data_ptr(), H
+            if j == K and dh_ext is not None:  # step t+1's input-state gradient (no episode ends here)
+                a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
+                a.dc_ext, a.ld_dcext = dc_ext.data_ptr(), H
+            if dc_next is not None:
+                a.dc, a.ld_dc = dc_next.data_ptr(), H
+            a.dgi, a.ld_dgi, a.dgh, a.ld_dgh = dgi.data_ptr(), 4 * H, dgh.data_ptr(), 4 * H
+            dco = None
+            if j > 0 or t > 0:  # the gradient w.r.t. the zero start state is not needed
+                dco = dc_buf[calls % 2]
+                a.dc_out, a.ld_dco = dco.data_ptr(), H
+            calls += 1
+            a.part = part.data_ptr()
+            if j > 0:
+                a.dgi_scale, a.dgi_max = sc_i.data_ptr(), mx["gi_upd"].data_ptr()
+            a.dgh_max = mx["gh_obs" if j == 0 else "gh_upd"].data_ptr()
+            if j > 0 or t > 0:
+                a.dgh_scale = sc_h.data_ptr()
+            L.check(lib.gm_lnlstm_cell_bwd(C.byref(a), L.stream_ptr()))
+            torch.sum(part, 0, out=psum[j, t])
+            if j > 0:
+                TS._dgrad(dgi, 4 * H, 4 * H, sc_i, wti_upd, M, H, H, None, 0, Dx, H)
+                TS._dgrad(dgh, 4 * H, 4 * H, sc_h, wth_upd, M, H, H, None, 0, Dh, H)
+            else:
+                if t < Ls - 1:
+                    dgi_sum.add_(dgi_t)
+                if t > 0:  # the h part = step t-1's state gradient
+                    dh0 = dh0_buf[t % 2]
+                    TS._dgrad(dgh, 4 * H, 4 * H, sc_h, wth_obs, M, H, H, None, 0, dh0, H)
+                    dh_ext, dc_ext = dh0, dco
+            dc_next = dco
+
+    # ---- the obs cell's x side on the summed dgi: W_ih's gradient and the encoder output's gradient ----
+    E, Eb = p.enc_out[-1], p.enc_bits[-1]
+    sa_sum = torch.empty(1, device=dev)
+    L.check(FU._setup().gm_absmax_scale(dgi_sum.data_ptr(), dgi_sum.numel(), sa_sum.data_ptr(), L.stream_ptr()))
+    gEs = torch.empty(1, M, H, device=dev)
+    partE = torch.empty(1, (M + 127) // 128, H, device=dev)
+    TS._dgrad(dgi_sum, 4 * H, 4 * H, sa_sum, wti_obs, M, H, H, Eb, Eb.stride(0), gEs[0], H, part=partE[0])
+    gwi = TS._wgrad(dgi_sum, sa_sum, E, H, p.s_obs)
+    # W_hh: step 0's h is zero; step t's is S[K, t-1] (contiguous over t = 1..L-1)
+    sa = {k: TS._finish(v) for k, v in mx.items()}
+    if Ls > 1:
+        gwh = TS._wgrad(dgh_obs[1:].reshape(-1, 4 * H), sa["gh_obs"], S[K, :Ls - 1].reshape(-1, S2), H, p.sh_obs)
+    else:
+        gwh = torch.zeros_like(co.weight_hh)
+    TS.lnl_param_grads(co, grads, gwi, gwh, psum[0].sum(0))
+    KLM = K * Ls * M
+    TS.lnl_param_grads(cu, grads, TS._wgrad(dgi_upd.view(KLM, 4 * H), sa["gi_upd"], p.agg.view(KLM, H), H, p.s_upd),
+                       TS._wgrad(dgh_upd.view(KLM, 4 * H), sa["gh_upd"], S[:K].reshape(KLM, S2), H, p.sh_upd),
+                       psum[1:].reshape(-1, 14 * H).sum(0))
+    return _encoder_bwd(p, gEs, partE, grads)
+
+
 def _forward(p):
     netmon = p.netmon
     if netmon.rnn_type == "gru":
         return _forward_gru(p)
+    if netmon.rnn_type == "lnlstm":
+        return _forward_lnl(p)
     X3d, nbr, Ls = p.x, p.nbr, p.steps
     dev = X3d.device
     B, N, F = X3d.shape
@@ -329,6 +514,8 @@ def _backward(p, dR):
     netmon = p.netmon
     if netmon.rnn_type == "gru":
         return _backward_gru(p, dR)
+    if netmon.rnn_type == "lnlstm":
+        return _backward_lnl(p, dR)
     Ls, B, N, F, H, K, M = p.dims
     S2 = 2 * H
     dev = dR.device

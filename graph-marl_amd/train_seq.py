@@ -21,13 +21,18 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
     wide, and a cell's h gradient arrives in two parts (dh_w through W4 and the direct g z), which
     the previous cell's call sums as two sources; the W4 weight gradient is mapped back to torch's
     weight_ih / weight_hh / bias layout (gru_param_grads);
+  * LayerNorm-LSTM cells (--netmon-rnn-type lnlstm, H <= 512) keep [h | c] state rows; per cell two no-bias GEMMs
+    (x W_ih^T, h W_hh^T) into saved raw products + gm_lnlstm_fwd (row statistics saved); the obs cell's x W_ih^T has
+    no recurrence and runs as ONE GEMM over all L steps' rows. Backward: gm_lnlstm_cell_bwd (sums the sources,
+    recomputes the activations, publishes the scales of dgi and dgh apart) and the input-gradient GEMMs dgh @ W_hh
+    and dgi @ W_ih, the obs cell's dgi @ W_ih once over all steps after the loop (_lnlstm_cells_bwd);
   * the leaky_relu derivative, the bias-gradient column sums and the gradient scales are fused
     into the kernels that produce the gradients (gm_gemm_x3_dgrad, gm_qhead_bwd,
-    gm_lstm_cell_bwd / gm_gru_cell_bwd), so no activation gradient is re-read for them.
+    gm_lstm_cell_bwd / gm_gru_cell_bwd / gm_lnlstm_cell_bwd), so no activation gradient is re-read for them.
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(LN-LSTM cells, no carry-over, global readout, aux loss, DGN/DQNR/CommNet, GM_GEMM=f32).
+(no carry-over, global readout, aux loss, DGN/DQNR/CommNet, GM_GEMM=f32).
 """
 import ctypes as C
 from collections import namedtuple
@@ -49,14 +54,16 @@ sequences `rows` (None = all)."""
 
 
 def cell_ok(netmon):
-    """lstm, or gru at a hidden size gm_gru_cell_bwd takes (H <= 256 dividing 256, or a multiple of 64)."""
+    """lstm, gru at a hidden size gm_gru_cell_bwd takes (H <= 256 dividing 256, or a multiple of 64), or lnlstm at
+    one gm_lnlstm_cell_bwd takes (H <= 512)."""
     H = netmon.hidden_features
-    return netmon.rnn_type == "lstm" or (netmon.rnn_type == "gru" and (256 % H == 0 or H % 64 == 0))
+    return (netmon.rnn_type == "lstm" or (netmon.rnn_type == "gru" and (256 % H == 0 or H % 64 == 0))
+            or (netmon.rnn_type == "lnlstm" and H <= 512))
 
 
 def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
-    """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM or GRU cells with
-    carry-over, sum / mean aggregation, neighbour readout, leaky MLPs, split-f16 GEMMs."""
+    """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM, GRU or LayerNorm-LSTM
+    cells with carry-over, sum / mean aggregation, neighbour readout, leaky MLPs, split-f16 GEMMs."""
     if netmon is None or aux_model is not None or att_coeff != 0 or L.GEMM_MODE != "x3":
         return False
     if type(model) is not MD.DQN or type(model_tar) is not MD.DQN:
@@ -189,6 +196,60 @@ def gru_param_grads(cell, grads, gx, gh, bg):
     grads[cell.bias_hh] = torch.cat([bg[:2 * H], bg[3 * H:]])
 
 
+def _lnl_x3t(cell):
+    """(X3 of W_ih^T [I][4H], X3 of W_hh^T [H][4H]) of a LayerNormLSTMCell for dx = dgi @ W_ih, dh = dgh @ W_hh."""
+    return _cache(cell).get("lnl_t", FU._key(cell.weight_ih, cell.weight_hh),
+                            lambda: (_x3(cell.weight_ih.detach().t().contiguous()),
+                                     _x3(cell.weight_hh.detach().t().contiguous())))
+
+
+def lnl_gemm(x, ldx, cell, hh, M, H, slot, G, ldg):
+    """Raw gate product of a LayerNormLSTMCell, no bias: G [M][4H] (row stride ldg) = x[:, :H] W_hh^T (hh) or
+    x W_ih^T, max |x| into slot."""
+    wp, ldw, x3 = FU.pack_lnlstm(cell)[1 if hh else 0]
+    FU.gemm(FU.dense(_ptr(x), ldx, H, amax=slot.data_ptr()), None, wp.data_ptr(), ldw, None, M, 4 * H, FU.GM_EPI_BIAS,
+            _ptr(G), ldg, x3=x3)
+
+
+def lnl_cell_fwd(cell, gi, ldgi, gh, ldgh, s_in, out, M, H, stats):
+    """gm_lnlstm_fwd on the raw products gi, gh and the c half of the [h | c] rows s_in: [h' | c'] into the rows
+    out (both 2H wide), the row statistics into stats [M][8]."""
+    li, lh, lc = cell.ln_input, cell.ln_hidden, cell.ln_cell
+    L.check(L.lib().gm_lnlstm_fwd(_ptr(gi), ldgi, _ptr(gh), ldgh, _ptr(s_in) + 4 * H, 2 * H, li.weight.data_ptr(),
+                                  li.bias.data_ptr(), lh.weight.data_ptr(), lh.bias.data_ptr(), cell.bias_ih.data_ptr(),
+                                  lc.weight.data_ptr(), lc.bias.data_ptr(), M, H, float(li.eps), _ptr(out), 2 * H,
+                                  _ptr(out) + 4 * H, 2 * H, stats.data_ptr(), L.stream_ptr()))
+
+
+LNL_RPW = 16  # rows per wave of gm_lnlstm_cell_bwd: one 14H partial row per 16 cell rows
+
+
+def lnl_bwd_args(cell, gi, ldgi, gh, ldgh, s_in, stats, M, H):
+    """gm_lnlstm_cell_bwd_args with the cell's saved forward operands filled in."""
+    li, lh, lc = cell.ln_input, cell.ln_hidden, cell.ln_cell
+    a = L.LNLSTMBwdArgs()
+    a.gi, a.ld_gi, a.gh, a.ld_gh = _ptr(gi), ldgi, _ptr(gh), ldgh
+    a.c_in, a.ld_cin = _ptr(s_in) + 4 * H, 2 * H
+    a.ln_in_w, a.ln_in_b, a.ln_hid_w, a.ln_hid_b = (t.data_ptr() for t in (li.weight, li.bias, lh.weight, lh.bias))
+    a.bias, a.ln_cell_w, a.ln_cell_b = cell.bias_ih.data_ptr(), lc.weight.data_ptr(), lc.bias.data_ptr()
+    a.eps, a.stats = float(li.eps), stats.data_ptr()
+    a.m, a.hidden, a.rows_per_wave = M, H, LNL_RPW
+    return a
+
+
+def lnl_param_grads(cell, grads, gwi, gwh, ps):
+    """The cell's parameter gradients from the two weight gradients and the summed 14H partials ps = [d ln_input.w |
+    d ln_hidden.w | d bias | d ln_cell.w | d ln_cell.b]; d ln_input.bias = d ln_hidden.bias = d bias_ih as separate
+    tensors (each may become a .grad modified in place)."""
+    H4 = 4 * cell.hidden_size
+    H = cell.hidden_size
+    grads[cell.weight_ih], grads[cell.weight_hh] = gwi, gwh
+    grads[cell.ln_input.weight], grads[cell.ln_hidden.weight] = ps[:H4], ps[H4:2 * H4]
+    db = ps[2 * H4:3 * H4]
+    grads[cell.bias_ih], grads[cell.ln_input.bias], grads[cell.ln_hidden.bias] = db, db.clone(), db.clone()
+    grads[cell.ln_cell.weight], grads[cell.ln_cell.bias] = ps[3 * H4:3 * H4 + H], ps[3 * H4 + H:]
+
+
 def _ptr(t):
     return t if isinstance(t, int) else t.data_ptr()
 
@@ -272,13 +333,39 @@ def _forward(p):
     # ---- recurrent cells, per step ----
     S_in = torch.empty(Ls, M, S2, device=dev)
     S = torch.empty(K + 1, Ls, M, S2, device=dev)  # cell outputs [h | c] (gru: h): j = 0 obs, 1..K update
-    act = torch.empty(K + 1, Ls, M, 4 * H, device=dev)  # gate activations (gru: G = [r | z | n | a_nh])
+    lnl = netmon.rnn_type == "lnlstm"
+    # gate activations (gru: G = [r | z | n | a_nh]); lnlstm keeps the raw gate products instead
+    act = None if lnl else torch.empty(K + 1, Ls, M, 4 * H, device=dev)
     agg = torch.empty(K, Ls, M, H, device=dev)
     s_obs, s_upd = _zeros1(dev), _zeros1(dev)
     keep = (~sb.episode_done).to(torch.float32)  # [L, B]
     S_in[0].copy_(sb.node_state.reshape(M, S2))
     lib = L.lib()
-    if gru:
+    if lnl:
+        # raw gate products: the obs cell's gi = E W_ih^T has no recurrence (its LayerNorm sees it alone), so ONE
+        # GEMM over all L steps' rows; gh and the update cell's [gi | gh] per step
+        co, cu = netmon.rnn_obs, netmon.rnn_update
+        p.gi_obs = torch.empty(Ls, M, 4 * H, device=dev)
+        p.gh_obs = torch.empty(Ls, M, 4 * H, device=dev)
+        p.g_upd = torch.empty(K, Ls, M, 8 * H, device=dev)
+        p.stats = torch.empty(K + 1, Ls, M, 8, device=dev)
+        p.sh_obs, p.sh_upd = _zeros1(dev), _zeros1(dev)  # max |h| of the two cells' h operands
+        lnl_gemm(E, H, co, False, LM, H, s_obs, p.gi_obs, 4 * H)
+        for t in range(Ls):
+            if t > 0:
+                torch.mul(S[K, t - 1].view(B, N * S2), keep[t - 1].view(B, 1), out=S_in[t].view(B, N * S2))
+            lnl_gemm(S_in[t], S2, co, True, M, H, p.sh_obs, p.gh_obs[t], 4 * H)
+            lnl_cell_fwd(co, p.gi_obs[t], 4 * H, p.gh_obs[t], 4 * H, S_in[t], S[0, t], M, H, p.stats[0, t])
+            for j in range(1, K + 1):
+                prev, G = S[j - 1, t], p.g_upd[j - 1, t]
+                L.check(lib.gm_mp_aggregate_rows(prev.data_ptr(), S2, nbr[t * B:(t + 1) * B].data_ptr(), B, N, deg,
+                                                 H, mean, agg[j - 1, t].data_ptr(), H, L.stream_ptr()))
+                lnl_gemm(agg[j - 1, t], H, cu, False, M, H, s_upd, G, 8 * H)
+                lnl_gemm(prev, S2, cu, True, M, H, p.sh_upd, G.data_ptr() + 16 * H, 8 * H)
+                lnl_cell_fwd(cu, G, 8 * H, G.data_ptr() + 16 * H, 8 * H, prev, S[j, t], M, H, p.stats[j, t])
+        _finish(p.sh_obs)
+        _finish(p.sh_upd)
+    elif gru:
         wo, wu = _gru_fwd(netmon.rnn_obs), _gru_fwd(netmon.rnn_update)
         for t in range(Ls):
             if t > 0:
@@ -448,6 +535,105 @@ def _gru_cells_bwd(p, dhf, dhp, grads):
     return gE, partE, gmaxE
 
 
+def _lnlstm_cells_bwd(p, dhf, dhp, grads):
+    """LayerNorm-LSTM cells of _backward, per step and cell in reverse: gm_lnlstm_cell_bwd (sums the cell's gradient
+    sources; writes dgi, dgh, the c gradient, parameter partials, the two scales and maxima), then the input
+    gradients dgh @ W_hh (h part) and, for the update cell, dgi @ W_ih (the previous cell's transposed-aggregate
+    source). The obs cell's dgi of all steps goes through W_ih and the encoder's last leaky mask in ONE GEMM after
+    the loop, on the scale finished from the accumulated max. Fills the cells' parameter gradients; returns (gE,
+    partE, gmaxE) for the batched encoder backward."""
+    netmon = p.netmon
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
+    S2 = 2 * H
+    dev = dhf.device
+    LM = Ls * M
+    lib = L.lib()
+    co, cu = netmon.rnn_obs, netmon.rnn_update
+    dgi_obs = torch.empty(Ls, M, 4 * H, device=dev)
+    dgh_obs = torch.empty(Ls, M, 4 * H, device=dev)
+    dgi_upd = torch.empty(K, Ls, M, 4 * H, device=dev)
+    dgh_upd = torch.empty(K, Ls, M, 4 * H, device=dev)
+    nw = (M + LNL_RPW - 1) // LNL_RPW
+    part = torch.empty(nw, 14 * H, device=dev)  # one call's per-wave partials, summed into psum right after it
+    psum = torch.empty(K + 1, Ls, 14 * H, device=dev)
+    mx = {k: _zeros1(dev) for k in ("gi_obs", "gh_obs", "gi_upd", "gh_upd")}
+    sc_i, sc_h = torch.empty(1, device=dev), torch.empty(1, device=dev)
+    (wti_obs, wth_obs), (wti_upd, wth_upd) = _lnl_x3t(co), _lnl_x3t(cu)
+    ep_done = p.seq.episode_done.to(torch.uint8).contiguous()  # [L, B]
+    Dx, Dh = torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)
+    dh0_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    # every cell's dc source is the dc output of the cell processed just before it: two buffers in turn
+    dc_buf = [torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)]
+    dh_ext = dc_ext = None
+    calls = 0
+    mean = int(netmon.agg_mode == 1)
+    deg = p.nbr.shape[-1]
+    for t in range(Ls - 1, -1, -1):
+        nbr_t = p.nbr[t * B:(t + 1) * B]
+        dc_next = None
+        for j in range(K, -1, -1):
+            if j == 0:
+                a = lnl_bwd_args(co, p.gi_obs[t], 4 * H, p.gh_obs[t], 4 * H, p.S_in[t], p.stats[0, t], M, H)
+                dgi, dgh = dgi_obs[t], dgh_obs[t]
+            else:
+                G = p.g_upd[j - 1, t]
+                a = lnl_bwd_args(cu, G, 8 * H, G.data_ptr() + 16 * H, 8 * H, p.S[j - 1, t], p.stats[j, t], M, H)
+                dgi, dgh = dgi_upd[j - 1, t], dgh_upd[j - 1, t]
+            if j == K:
+                a.dh0, a.ld_dh0 = dhf[t * M:(t + 1) * M].data_ptr(), H
+            else:
+                a.dh0, a.ld_dh0 = Dh.data_ptr(), H  # h part of the next cell's input gradient
+                a.dm, a.ld_dm = Dx.data_ptr(), H    # its aggregate part, transposed
+                a.nbr, a.n_nodes, a.deg, a.mean = nbr_t.data_ptr(), N, deg, mean
+            if j == K - 1:
+                a.dh1, a.ld_dh1 = dhp[t * M:(t + 1) * M].data_ptr(), H
+            if j == K and dh_ext is not None:  # step t+1's input-state gradient, zero where episode t ended
+                a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
+                a.dc_ext, a.ld_dcext = dc_ext.data_ptr(), H
+                a.ext_mask, a.rows_per_sample = ep_done[t].data_ptr(), N
+            if dc_next is not None:
+                a.dc, a.ld_dc = dc_next.data_ptr(), H
+            a.dgi, a.ld_dgi, a.dgh, a.ld_dgh = dgi.data_ptr(), 4 * H, dgh.data_ptr(), 4 * H
+            dco = None
+            if j > 0 or t > 0:  # the gradient w.r.t. the replayed start state is not needed
+                dco = dc_buf[calls % 2]
+                a.dc_out, a.ld_dco = dco.data_ptr(), H
+            calls += 1
+            a.part = part.data_ptr()
+            a.dgi_max = mx["gi_obs" if j == 0 else "gi_upd"].data_ptr()
+            a.dgh_max = mx["gh_obs" if j == 0 else "gh_upd"].data_ptr()
+            if j > 0:
+                a.dgi_scale = sc_i.data_ptr()
+            if j > 0 or t > 0:
+                a.dgh_scale = sc_h.data_ptr()
+            L.check(lib.gm_lnlstm_cell_bwd(C.byref(a), L.stream_ptr()))
+            torch.sum(part, 0, out=psum[j, t])
+            if j > 0:
+                _dgrad(dgi, 4 * H, 4 * H, sc_i, wti_upd, M, H, H, None, 0, Dx, H)
+                _dgrad(dgh, 4 * H, 4 * H, sc_h, wth_upd, M, H, H, None, 0, Dh, H)
+            elif t > 0:  # the h part = step t-1's state gradient
+                dh0 = dh0_buf[t % 2]
+                _dgrad(dgh, 4 * H, 4 * H, sc_h, wth_obs, M, H, H, None, 0, dh0, H)
+                dh_ext, dc_ext = dh0, dco
+            dc_next = dco
+    sa = {k: _finish(v) for k, v in mx.items()}
+    # the obs cell's x gradient of all steps through the encoder's last leaky_relu (bias partials and max for the
+    # batched encoder backward)
+    E, Eb = p.enc_out[-1], p.enc_bits[-1]
+    gE = torch.empty(LM, H, device=dev)
+    partE = torch.empty((LM + 127) // 128, H, device=dev)
+    gmaxE = _zeros1(dev)
+    _dgrad(dgi_obs, 4 * H, 4 * H, sa["gi_obs"], wti_obs, LM, H, H, Eb, Eb.stride(0), gE, H, part=partE, gmax=gmaxE)
+    # weight gradients over all steps (and update iterations), each operand with its own scale
+    lnl_param_grads(co, grads, _wgrad(dgi_obs.view(LM, 4 * H), sa["gi_obs"], E, H, p.s_obs),
+                    _wgrad(dgh_obs.view(LM, 4 * H), sa["gh_obs"], p.S_in.view(LM, S2), H, p.sh_obs),
+                    psum[0].sum(0))
+    lnl_param_grads(cu, grads, _wgrad(dgi_upd.view(K * LM, 4 * H), sa["gi_upd"], p.agg.view(K * LM, H), H, p.s_upd),
+                    _wgrad(dgh_upd.view(K * LM, 4 * H), sa["gh_upd"], p.S[:K].reshape(K * LM, S2), H, p.sh_upd),
+                    psum[1:].reshape(-1, 14 * H).sum(0))
+    return gE, partE, gmaxE
+
+
 def _backward(p, dq):
     netmon, dqn = p.netmon, p.dqn
     Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
@@ -509,6 +695,8 @@ def _backward(p, dq):
     # ---- recurrent cells, per step, in reverse ----
     if netmon.rnn_type == "gru":
         gE, partE, gmaxE = _gru_cells_bwd(p, dhf, dhp, grads)
+    elif netmon.rnn_type == "lnlstm":
+        gE, partE, gmaxE = _lnlstm_cells_bwd(p, dhf, dhp, grads)
     else:
         dG = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
         rpb_c = 64

@@ -383,6 +383,49 @@ typedef struct {
     float* dg_max;
 } gm_gru_bwd_args;
 int gm_gru_cell_bwd(const gm_gru_bwd_args* a, void* stream);
+/* LayerNorm-LSTM cell backward of the sequence-batched training path (LayerNormLSTMCell,
+ * src/layernormlstm.py:24-42, backward of torch autograd): gm_lnlstm_bwd with the cell's gradient sources
+ * summed on the fly as gm_lstm_cell_bwd sums them. Per row r and unit u, with the saved raw gate products
+ * gi = x W_ih^T, gh = h W_hh^T ([m][4H] strided, gate order i, f, g, o), the cell input c_in (strided, the c
+ * half of an [h | c] row), the seven parameter vectors of gm_lnlstm_fwd, its eps and its stats[m][8]:
+ *   dh  = dh0 + dh1 + sum_{n in {r} U nbr(r)} dm[n] s(n) + (ext_mask[r / rows_per_sample] ? 0 : dh_ext)
+ *   dc' = dc + (ext_mask[...] ? 0 : dc_ext)
+ * (every source nullable; dm = the input gradient of the aggregate input of the next cell, s(n) = 1 or
+ * 1 / |{n} U nbr(n)| for mean, -1 entries skipped), then gm_lnlstm_bwd's row math on (dh, dc'), recomputed
+ * from gi, gh, c_in and stats (eps is already inside the saved 1 / std; no activation tensor is read): writes
+ * dgi, dgh ([m][4H] strided, columns >= 4H untouched), dc_out = d c_in [m][H] (nullable), per-wave
+ * parameter-gradient partials part [ceil(m / rows_per_wave)][14H] in gm_lnlstm_bwd's layout (nullable;
+ * rows_per_wave default 8), and for each of dgi and dgh (the A operands of different GEMMs) max |.| as a
+ * power-of-two scale (dgi_scale / dgh_scale, gm_absmax_scale semantics, nullable) and as float bits
+ * accumulated by atomicMax (dgi_max / dgh_max, nullable). With a single dh0 and / or dc source the outputs are
+ * gm_lnlstm_bwd's bit for bit at the same rows_per_wave. H <= 512; any other H: GM_ERR_UNSUPPORTED, nothing
+ * launched. */
+typedef struct {
+    const float* gi; int64_t ld_gi;
+    const float* gh; int64_t ld_gh;
+    const float* c_in; int64_t ld_cin;
+    const float *ln_in_w, *ln_in_b, *ln_hid_w, *ln_hid_b, *bias, *ln_cell_w, *ln_cell_b;
+    float eps;
+    const float* stats;
+    const float* dh0; int64_t ld_dh0;
+    const float* dh1; int64_t ld_dh1;
+    const float* dm; int64_t ld_dm;
+    const int32_t* nbr; int32_t n_nodes, deg, mean;
+    const float* dh_ext; int64_t ld_ext;
+    const float* dc_ext; int64_t ld_dcext;
+    const uint8_t* ext_mask; int32_t rows_per_sample;
+    const float* dc; int64_t ld_dc;
+    int32_t m, hidden;
+    float* dgi; int64_t ld_dgi;
+    float* dgh; int64_t ld_dgh;
+    float* dc_out; int64_t ld_dco;
+    float* part; int32_t rows_per_wave;
+    float* dgi_scale;
+    float* dgi_max;
+    float* dgh_scale;
+    float* dgh_max;
+} gm_lnlstm_cell_bwd_args;
+int gm_lnlstm_cell_bwd(const gm_lnlstm_cell_bwd_args* a, void* stream);
 /* Q head + last hidden layer backward (Q_Net.fc after a leaky_relu MLP layer, src/model.py:119-125,
  * 187-203): g[r][c] = (sum_a dq[r][a] wq[a][c]) * (act && y[r][c] <= 0 ? 0.01 : 1) for the layer
  * output y; per block of rows_per_block rows: part_b[blk][c] = sum g (the layer's bias gradient),

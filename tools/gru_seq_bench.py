@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
-"""GRU NetMon training: the sequence-batched paths against the per-step autograd paths, interleaved in one
-process.
+"""GRU / LN-LSTM NetMon training (--rnn-type gru | lnlstm | lstm): the sequence-batched paths against the per-step
+autograd paths, interleaved in one process.
 
   update:  one DQN + NetMon update at bench.py's training shape (4096 envs, N = 20, H = 128, K = 1,
            13 108 sequences x 8 steps) on train_seq.dqn_update_seq and on train.dqn_update, sampling included.
            Rounds alternate A (sequence-batched) and B (autograd); each round times `--reps` updates between
            device synchronisations; the medians over the rounds are reported.
-  config5: src/sl.py's iteration (N = 100, batch 8192, sequence length 8, K = 1) with --netmon-rnn-type gru on
+  config5: src/sl.py's iteration (N = 100, batch 8192, sequence length 8, K = 1) with --netmon-rnn-type <rnn-type> on
            sl_seq and with --sl-autograd, alternating whole sl.main(--bench) runs.
 
-Prints one JSON line. Usage: python tools/gru_seq_bench.py [--rounds 3] [--reps 3] [--skip-config5]
+Prints one JSON line. Usage: python tools/gru_seq_bench.py [--rnn-type gru] [--rounds 3] [--reps 3] [--skip-config5]
 """
 import argparse
 import copy
@@ -90,6 +90,9 @@ def config5_pair(a):
     base = ["--bench", "--n-nodes", "100", "--batch-size", "8192", "--sequence-length", "8", "--netmon-iterations",
             "1", "--netmon-rnn-type", a.rnn_type, "--iterations", "3", "--warmup", "2"]
     ms = {"seq": [], "autograd": []}
+    if a.rnn_type not in SL.SEQ_RNN_TYPES:  # a cell type sl.py keeps on the autograd path: time its unroll anyway
+        assert SL.SQ.TS.cell_ok(argparse.Namespace(rnn_type=a.rnn_type, hidden_features=128))
+        SL.SEQ_RNN_TYPES += (a.rnn_type,)
     for _ in range(max(1, a.rounds - 1)):
         ms["seq"].append(SL.main(base, quiet=True)["ms_per_iteration"])
         torch.cuda.empty_cache()
@@ -104,7 +107,7 @@ def main():
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--n-env", type=int, default=4096)
-    p.add_argument("--rnn-type", default="gru", choices=["gru", "lstm"])
+    p.add_argument("--rnn-type", default="gru", choices=["gru", "lnlstm", "lstm"])
     p.add_argument("--skip-config5", action="store_true")
     a = p.parse_args()
     out = {"update": update_pair(a)}
