@@ -35,7 +35,7 @@ EXPORTS = [
     "gm_gemm_x3_dgrad", "gm_lstm_cell_bwd", "gm_qhead_bwd", "gm_netmon_readout_ld", "gm_routing_node_encoder_bits", "gm_gather_records",
     "gm_lnlstm_fwd", "gm_lnlstm_bwd", "gm_gru_pointwise", "gm_gru_bwd", "gm_act_bwd", "gm_build_info",
     "gm_act_fwd", "gm_act_bwd_z", "gm_obs_from_gemm", "gm_encoder_x3", "gm_step_mse_blocks", "gm_step_mse",
-    "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd",
+    "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd", "gm_agent_comm_bwd",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
@@ -214,6 +214,7 @@ def lib():
         "gm_gru_cell_fwd": [vp, i64, vp, i64, i32, i32, vp, i64, vp],
         "gm_gru_cell_bwd": [C.POINTER(GRUBwdArgs), vp],
         "gm_lnlstm_cell_bwd": [C.POINTER(LNLSTMBwdArgs), vp],
+        "gm_agent_comm_bwd": [vp, i64, vp, i64, vp, i32, i32, i32, vp, i64, vp],
     }
     for name, at in newer.items():
         if hasattr(L, name) or not os.environ.get("GM_LIB"):

@@ -57,6 +57,7 @@ W = importlib.import_module("graph-marl_amd.wrapper")
 P = importlib.import_module("graph-marl_amd.policy")
 T = importlib.import_module("graph-marl_amd.train")
 TS = importlib.import_module("graph-marl_amd.train_seq")
+AS = importlib.import_module("graph-marl_amd.agent_seq")
 RB = importlib.import_module("graph-marl_amd.replaybuffer")
 S = importlib.import_module("graph-marl_amd.simple")
 HEU = importlib.import_module("graph-marl_amd.heuristics")
@@ -478,6 +479,13 @@ def _main(args, rank, world):
                                                         buff.get_sequences(args.mini_batch_size,
                                                                            args.sequence_length),
                                                         args.gamma, args.tau, args.target_update_steps, iteration)
+                qs, qts = list(q_all), list(qt_all)
+            elif args.sequence_length > 1 and AS.agent_seq_ok(model, model_tar, netmon, att, aux_model, n_agents):
+                # DQNR / CommNet without NetMon: the sequence-batched update of agent_seq.py
+                loss, q_all, qt_all = AS.agent_update_seq(model, model_tar, optimizer, params,
+                                                          buff.get_agent_sequences(args.mini_batch_size,
+                                                                                   args.sequence_length),
+                                                          args.gamma, args.tau, args.target_update_steps, iteration)
                 qs, qts = list(q_all), list(qt_all)
             else:
                 batches = list(buff.get_batch(args.mini_batch_size, sequence_length=args.sequence_length,

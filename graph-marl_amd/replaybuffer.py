@@ -231,6 +231,34 @@ class ReplayBuffer:
                         self.agent_node[slots, envs].int().contiguous(), self._records(self.node_state, first, env),
                         next_fields, (slots, env))
 
+    def get_agent_sequences(self, batch_size, sequence_length):
+        """The sequences get_batch(batch_size, sequence_length) draws (same stream, same indices), as one
+        agent_seq.AgentSeqBatch for the models with an agent state and no NetMon (DQNR, CommNet): every step's
+        fields stacked ([L, B, ...], one gather per field), the stored next observations (and next adjacency)
+        in full, since the target model reads them at every step, the adjacencies as int8, and the agent state
+        of each sequence's first slot."""
+        from .agent_seq import AgentSeqBatch
+
+        if self.agent_state is None:
+            raise ValueError("get_agent_sequences: the buffer stores no agent state")
+        if self.count <= sequence_length:
+            raise ValueError("not enough transitions for the requested sequence length")
+        Lq = sequence_length
+        span = self.count - Lq
+        f = self.choice(self.n_env * span, batch_size)
+        env = f // span
+        first = (self.index % self.count + f % span) % self.count
+        slots = (first.unsqueeze(0) + torch.arange(Lq, device=f.device).unsqueeze(1)) % self.count  # [L, B]
+        envs = env.unsqueeze(0).expand(Lq, -1)
+        i8 = torch.int8
+        return AgentSeqBatch(self._records(self.obs, slots, env), self.obs_dim, self.action[slots, envs].long(),
+                             self.reward[slots, envs].to(torch.float32), self.done[slots, envs],
+                             self.episode_done[slots],
+                             self.adj[slots, envs].to(i8) if self.adj is not None else None,
+                             self._records(self.next_obs, slots, env),
+                             self.next_adj[slots, envs].to(i8) if self.next_adj is not None else None,
+                             self._records(self.agent_state, first, env), (slots, env))
+
     @staticmethod
     def _records(src, slots, env):
         """src[slots, env] as float32 (slots [..., B'] int64 slot indices, env [B'] env indices): one

@@ -31,6 +31,7 @@
  *                                    Q_Net.fc (torch autograd of the update, src/main.py:996)
  *   gm_agent_attention               AttModel attention core (DGN)          src/model.py:86-117
  *   gm_agent_comm                    CommNet communication step             src/model.py:780-787
+ *   gm_agent_comm_bwd                its transpose (sequence-batched training of CommNet)
  */
 #ifndef GRAPH_MARL_AMD_H
 #define GRAPH_MARL_AMD_H
@@ -620,6 +621,15 @@ int gm_agent_attention(const float* q, const float* k, const float* v, int64_t l
  * h_j / max(count, 1) per env; h, out rows [B*A][ldh / ldo] (out must not alias h). */
 int gm_agent_comm(const float* h, int64_t ldh, const int8_t* adj, int32_t B, int32_t A, int32_t H, float* out,
                   int64_t ldo, void* stream);
+/* Its transpose (backward of torch autograd through CommNet's communication step): with g = g0 + g1,
+ *   dh_j = g_j + sum_{i != j, adj_ij} g_i / max(cnt_i, 1),   cnt_i = |{k != i : adj_ik}|
+ * per env, summed over i ascending in fp32; the diagonal of adj is ignored whatever it holds, adj need not be
+ * symmetric. g0, g1 (nullable), dh: rows [B*A][ld0 / ld1 / ldd] (g0 and g1 are the x and h halves of a comm-round
+ * LSTM cell's [dx | dh] input gradient: the cell's x and h are the same tensor); dh must not alias g0 or g1.
+ * 16-byte lanes when H % 4 == 0 and every base and stride allows, scalar otherwise. A <= 64, H <= 1024; anything
+ * else: GM_ERR_UNSUPPORTED, nothing launched. */
+int gm_agent_comm_bwd(const float* g0, int64_t ld0, const float* g1, int64_t ld1, const int8_t* adj, int32_t B,
+                      int32_t A, int32_t H, float* dh, int64_t ldd, void* stream);
 
 /* Build provenance: "src=<16 hex digits of the SHA-256 of the csrc sources and headers> arch=<gfx> hipcc=<version>",
  * fixed when the library is linked (tests/test_capi.py checks it against the tree; bench.py reports it). */
