@@ -24,7 +24,8 @@ one autograd node over the whole sequence (`_AgentSeqFn`), organised like train_
     the obs cell's dx rows of all steps land in one buffer, masked by the encoder's last leaky derivative, for the
     batched encoder backward.
 
-Every other configuration (NetMon, DGN, aux loss, attention regularisation, GM_GEMM=f32) keeps train.dqn_loss.
+Every other configuration (NetMon, aux loss, GM_GEMM=f32) keeps train.dqn_loss; DGN without NetMon, attention
+regularisation included, has its own batched update (dgn_seq.py).
 """
 import ctypes as C
 from collections import namedtuple

@@ -201,6 +201,308 @@ __global__ __launch_bounds__(256) void k_agent_comm_bwd(const float* __restrict_
     }
 }
 
+// Transpose of the k_agent_attention core (gm_agent_attention_bwd) for one env per block. With, per (agent i, head),
+//   w_ij = <q_i, k_j> / sqrt(dk),  p_i. = softmax_j(adj_ij ? w_ij : -1e9),  dP_ij = <dout_i, v_j>,
+//   Ds_i = sum_j p_ij dP_ij,       dw_ij = adj_ij ? p_ij (dP_ij - Ds_i) : 0    (masked_fill passes no gradient),
+// and, with the regulariser (REG: the target model's q_tar / k_tar rows, row scale r, 1 when null),
+//   dw_ij += r_i (softmax_j(w_i.) - softmax_j(w_tar,i.))_j                     over ALL j (unmasked softmaxes),
+// the outputs are dq_i = sum_j dw_ij k_j / sqrt(dk), dk_j = sum_i dw_ij q_i / sqrt(dk), dv_j = sum_i p_ij dout_i +
+// dout_j (skip connection). Phase 1 stages the env's k, v (and k_tar) rows and adj in LDS: a thread owns (i, head),
+// reads its own q_i, dout_i (q_tar,i) rows from HBM, keeps the row statistics (max, 1 / sum, Ds; REG: the two
+// unmasked softmaxes' max and 1 / sum, r_i) in LDS and writes dq_i. Phase 2 stages q, dout (and q_tar) over the same
+// LDS: a thread owns (j, head), reads its own k_j, v_j (k_tar,j) rows, recomputes p_ij and dw_ij from the statistics
+// for i ascending and sums dk_j, dv_j in fp32 registers: no A x A array anywhere, no atomics, the same bits on every
+// run. LDS per env: A heads ((REG ? 2 : 1) dk + dv + (REG ? 8 : 3)) floats + A^2 bytes (37 KB at A = 20, 8 heads,
+// d = 16 with the regulariser: 4 envs per CU). Plain vector stores.
+template <int D, bool REG>
+__global__ __launch_bounds__(256) void k_agent_attention_bwd(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, long long ld,
+    const int8_t* __restrict__ adj, int A, int heads, int dk_, int dv_, float scale, const float* __restrict__ dout,
+    long long ldo, const float* __restrict__ qt, const float* __restrict__ kt, long long ldt,
+    const float* __restrict__ r, float* __restrict__ dq, float* __restrict__ dkk, float* __restrict__ dvv,
+    long long ldd) {
+    constexpr int RD = D > 0 ? D : MAXD;
+    constexpr int NS = REG ? 8 : 3;
+    const int dk = D > 0 ? D : dk_, dv = D > 0 ? D : dv_;
+    extern __shared__ float sm[];
+    const int b = blockIdx.x;
+    const int KD = heads * dk, VD = heads * dv;
+    float* ks = sm;               // [A][KD]  phase 1: k,     phase 2: q
+    float* vs = ks + A * KD;      // [A][VD]  phase 1: v,     phase 2: dout
+    float* kts = vs + A * VD;     // [A][KD]  phase 1: k_tar, phase 2: q_tar (REG)
+    float* st = kts + (REG ? A * KD : 0);  // [A * heads][NS]
+    int8_t* sadj = reinterpret_cast<int8_t*>(st + A * heads * NS);
+    float *qs = ks, *ds = vs, *qts = kts;
+    const long long row0 = (long long)b * A;
+    for (int idx = threadIdx.x; idx < A * KD; idx += blockDim.x) {
+        const int j = idx / KD, c = idx - j * KD;
+        ks[idx] = k[(row0 + j) * ld + c];
+        if (REG) kts[idx] = kt[(row0 + j) * ldt + c];
+    }
+    for (int idx = threadIdx.x; idx < A * VD; idx += blockDim.x) {
+        const int j = idx / VD, c = idx - j * VD;
+        vs[idx] = v[(row0 + j) * ld + c];
+    }
+    for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x) sadj[idx] = adj[row0 * A + idx];
+    __syncthreads();
+
+    // ---- phase 1: (i, head) rows: statistics and dq_i ----
+    for (int p = threadIdx.x; p < A * heads; p += blockDim.x) {
+        const int i = p / heads, h = p - i * heads;
+        float qi[RD], di[RD];
+#pragma unroll
+        for (int d = 0; d < RD; d++) {
+            if (d < dk) qi[d] = q[(row0 + i) * ld + h * dk + d];
+            if (d < dv) di[d] = dout[(row0 + i) * ldo + h * dv + d];
+        }
+        // (REG) the thread's own q_tar row: registers at the compile-time width, read in place otherwise
+        float qtr[D > 0 ? D : 1];
+        const float* qti = REG ? qt + (row0 + i) * ldt + h * dk : nullptr;
+        if constexpr (D > 0 && REG) {
+#pragma unroll
+            for (int d = 0; d < D; d++) qtr[d] = qti[d];
+            qti = qtr;
+        }
+        const int8_t* ai = sadj + i * A;
+        float mx = -INFINITY, mxu = -INFINITY, mxt = -INFINITY;
+        for (int j = 0; j < A; j++) {
+            const float* kj = ks + j * KD + h * dk;
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) s = fmaf(qi[d], kj[d], s);
+            s *= scale;
+            mx = fmaxf(mx, ai[j] ? s : -1e9f);
+            if (REG) {
+                const float* ktj = kts + j * KD + h * dk;
+                float t = 0.f;
+#pragma unroll
+                for (int d = 0; d < RD; d++)
+                    if (d < dk) t = fmaf(qti[d], ktj[d], t);
+                mxu = fmaxf(mxu, s);
+                mxt = fmaxf(mxt, t * scale);
+            }
+        }
+        float sum = 0.f, num = 0.f, sumu = 0.f, sumt = 0.f;
+        for (int j = 0; j < A; j++) {
+            const float* kj = ks + j * KD + h * dk;
+            const float* vj = vs + j * VD + h * dv;
+            float s = 0.f, dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) s = fmaf(qi[d], kj[d], s);
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dv) dp = fmaf(di[d], vj[d], dp);
+            s *= scale;
+            const float e = expf((ai[j] ? s : -1e9f) - mx);
+            sum += e;
+            num = fmaf(e, dp, num);
+            if (REG) {
+                const float* ktj = kts + j * KD + h * dk;
+                float t = 0.f;
+#pragma unroll
+                for (int d = 0; d < RD; d++)
+                    if (d < dk) t = fmaf(qti[d], ktj[d], t);
+                sumu += expf(s - mxu);
+                sumt += expf(t * scale - mxt);
+            }
+        }
+        const float inv = 1.0f / sum, Ds = num * inv;
+        const float invu = REG ? 1.0f / sumu : 0.f, invt = REG ? 1.0f / sumt : 0.f;
+        const float ri = REG ? (r ? r[row0 + i] : 1.0f) : 0.f;
+        float* sp = st + p * NS;
+        sp[0] = mx;
+        sp[1] = inv;
+        sp[2] = Ds;
+        if (REG) {
+            sp[3] = mxu;
+            sp[4] = invu;
+            sp[5] = mxt;
+            sp[6] = invt;
+            sp[7] = ri;
+        }
+        float acc[RD];
+#pragma unroll
+        for (int d = 0; d < RD; d++) acc[d] = 0.f;
+        for (int j = 0; j < A; j++) {
+            const float* kj = ks + j * KD + h * dk;
+            const float* vj = vs + j * VD + h * dv;
+            float s = 0.f, dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) s = fmaf(qi[d], kj[d], s);
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dv) dp = fmaf(di[d], vj[d], dp);
+            s *= scale;
+            float dw = 0.f;
+            if (ai[j]) dw = expf(s - mx) * inv * (dp - Ds);
+            if (REG) {
+                const float* ktj = kts + j * KD + h * dk;
+                float t = 0.f;
+#pragma unroll
+                for (int d = 0; d < RD; d++)
+                    if (d < dk) t = fmaf(qti[d], ktj[d], t);
+                dw += ri * (expf(s - mxu) * invu - expf(t * scale - mxt) * invt);
+            }
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) acc[d] = fmaf(dw, kj[d], acc[d]);
+        }
+        float* o = dq + (row0 + i) * ldd + h * dk;
+#pragma unroll
+        for (int d = 0; d < RD; d++)
+            if (d < dk) o[d] = acc[d] * scale;
+    }
+    __syncthreads();
+
+    // ---- phase 2: q, dout (q_tar) over the rows phase 1 read; (j, head) columns: dk_j, dv_j over i ascending ----
+    for (int idx = threadIdx.x; idx < A * KD; idx += blockDim.x) {
+        const int j = idx / KD, c = idx - j * KD;
+        qs[idx] = q[(row0 + j) * ld + c];
+        if (REG) qts[idx] = qt[(row0 + j) * ldt + c];
+    }
+    for (int idx = threadIdx.x; idx < A * VD; idx += blockDim.x) {
+        const int j = idx / VD, c = idx - j * VD;
+        ds[idx] = dout[(row0 + j) * ldo + c];
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < A * heads; p += blockDim.x) {
+        const int j = p / heads, h = p - j * heads;
+        float kj[RD], vj[RD], ak[RD], av[RD];
+#pragma unroll
+        for (int d = 0; d < RD; d++) {
+            if (d < dk) kj[d] = k[(row0 + j) * ld + h * dk + d];
+            if (d < dv) vj[d] = v[(row0 + j) * ld + h * dv + d];
+            ak[d] = 0.f;
+            av[d] = 0.f;
+        }
+        float ktr[D > 0 ? D : 1];
+        const float* ktj = REG ? kt + (row0 + j) * ldt + h * dk : nullptr;
+        if constexpr (D > 0 && REG) {
+#pragma unroll
+            for (int d = 0; d < D; d++) ktr[d] = ktj[d];
+            ktj = ktr;
+        }
+        for (int i = 0; i < A; i++) {
+            const float* qi = qs + i * KD + h * dk;
+            const float* di = ds + i * VD + h * dv;
+            const float* sp = st + (i * heads + h) * NS;
+            float s = 0.f, dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) s = fmaf(qi[d], kj[d], s);
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dv) dp = fmaf(di[d], vj[d], dp);
+            s *= scale;
+            const bool a = sadj[i * A + j] != 0;
+            const float pij = expf((a ? s : -1e9f) - sp[0]) * sp[1];
+            float dw = a ? pij * (dp - sp[2]) : 0.f;
+            if (REG) {
+                const float* qti = qts + i * KD + h * dk;
+                float t = 0.f;
+#pragma unroll
+                for (int d = 0; d < RD; d++)
+                    if (d < dk) t = fmaf(qti[d], ktj[d], t);
+                dw += sp[7] * (expf(s - sp[3]) * sp[4] - expf(t * scale - sp[5]) * sp[6]);
+            }
+#pragma unroll
+            for (int d = 0; d < RD; d++) {
+                if (d < dk) ak[d] = fmaf(dw, qi[d], ak[d]);
+                if (d < dv) av[d] = fmaf(pij, di[d], av[d]);
+            }
+        }
+        float* ok = dkk + (row0 + j) * ldd + h * dk;
+        float* ov = dvv + (row0 + j) * ldd + h * dv;
+        const float* dj = ds + j * VD + h * dv;
+#pragma unroll
+        for (int d = 0; d < RD; d++) {
+            if (d < dk) ok[d] = ak[d] * scale;
+            if (d < dv) ov[d] = av[d] + dj[d];
+        }
+    }
+}
+
+// Forward value of DGN's attention regulariser (gm_agent_attention_kl) for one env per block:
+//   kl_row[i] = sum_heads sum_j t_ij (log t_ij - log p_ij),  p = softmax_j(w_i.), t = softmax_j(w_tar,i.)
+// (both unmasked), heads and j ascending. Both score rows are recomputed from the k / k_tar rows staged in LDS:
+//   sum_j t_j (log t_j - log p_j) = sum_j e^{a_j} (a_j - b_j) / sum_j e^{a_j} + log sum_j e^{b_j} - log sum_j e^{a_j}
+// with a = w_tar - max w_tar, b = w - max w.
+template <int D>
+__global__ __launch_bounds__(256) void k_agent_attention_kl(const float* __restrict__ q, const float* __restrict__ k,
+                                                            long long ld, const float* __restrict__ qt,
+                                                            const float* __restrict__ kt, long long ldt, int A,
+                                                            int heads, int dk_, float scale,
+                                                            float* __restrict__ kl_row) {
+    constexpr int RD = D > 0 ? D : MAXD;
+    const int dk = D > 0 ? D : dk_;
+    extern __shared__ float sm[];
+    const int b = blockIdx.x;
+    const int KD = heads * dk;
+    float* ks = sm;             // [A][KD]
+    float* kts = ks + A * KD;   // [A][KD]
+    float* klh = kts + A * KD;  // [A][heads]
+    const long long row0 = (long long)b * A;
+    for (int idx = threadIdx.x; idx < A * KD; idx += blockDim.x) {
+        const int j = idx / KD, c = idx - j * KD;
+        ks[idx] = k[(row0 + j) * ld + c];
+        kts[idx] = kt[(row0 + j) * ldt + c];
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < A * heads; p += blockDim.x) {
+        const int i = p / heads, h = p - i * heads;
+        float qi[RD], qti[RD];
+        const float* qr = q + (row0 + i) * ld + h * dk;
+        const float* qtr = qt + (row0 + i) * ldt + h * dk;
+#pragma unroll
+        for (int d = 0; d < RD; d++)
+            if (d < dk) {
+                qi[d] = qr[d];
+                qti[d] = qtr[d];
+            }
+        float mxu = -INFINITY, mxt = -INFINITY;
+        for (int j = 0; j < A; j++) {
+            const float* kj = ks + j * KD + h * dk;
+            const float* ktj = kts + j * KD + h * dk;
+            float s = 0.f, t = 0.f;
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) {
+                    s = fmaf(qi[d], kj[d], s);
+                    t = fmaf(qti[d], ktj[d], t);
+                }
+            mxu = fmaxf(mxu, s * scale);
+            mxt = fmaxf(mxt, t * scale);
+        }
+        float su = 0.f, stt = 0.f, num = 0.f;
+        for (int j = 0; j < A; j++) {
+            const float* kj = ks + j * KD + h * dk;
+            const float* ktj = kts + j * KD + h * dk;
+            float s = 0.f, t = 0.f;
+#pragma unroll
+            for (int d = 0; d < RD; d++)
+                if (d < dk) {
+                    s = fmaf(qi[d], kj[d], s);
+                    t = fmaf(qti[d], ktj[d], t);
+                }
+            const float bj = s * scale - mxu, aj = t * scale - mxt;
+            const float ea = expf(aj);
+            su += expf(bj);
+            stt += ea;
+            num = fmaf(ea, aj - bj, num);
+        }
+        klh[p] = num / stt + (logf(su) - logf(stt));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < A; i += blockDim.x) {
+        float s = 0.f;
+        for (int h = 0; h < heads; h++) s += klh[i * heads + h];
+        kl_row[row0 + i] = s;
+    }
+}
+
 int launched(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gm_fail(GM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -252,4 +554,72 @@ extern "C" int gm_agent_comm_bwd(const float* g0, int64_t ld0, const float* g1, 
         hipLaunchKernelGGL(k_agent_comm_bwd<1>, grid, dim3(256), 0, (hipStream_t)stream, g0, (long long)ld0, g1,
                            (long long)ld1, adj, A, H, dh, (long long)ldd);
     return launched("gm_agent_comm_bwd");
+}
+
+// LDS bytes of k_agent_attention_bwd: the k, v (and k_tar) rows, then q, dout (q_tar) over them; the row statistics, adj
+static size_t attention_bwd_lds(int A, int heads, int dk, int dv, bool reg) {
+    const size_t fl = (size_t)A * heads * ((reg ? 2 : 1) * (size_t)dk + (size_t)dv + (reg ? 8 : 3));
+    return fl * sizeof(float) + (((size_t)A * A + 15) & ~(size_t)15);
+}
+
+template <typename K>
+static bool lds_opt_in(K kern, size_t lds) {
+    return lds <= 64 * 1024 ||
+           hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+}
+
+extern "C" int gm_agent_attention_bwd(const float* q, const float* k, const float* v, int64_t ld, const int8_t* adj,
+                                      int32_t B, int32_t A, int32_t heads, int32_t dk, int32_t dv, const float* dout,
+                                      int64_t ldo, const float* q_tar, const float* k_tar, int64_t ld_tar,
+                                      const float* r, float* dq, float* dk_out, float* dv_out, int64_t ldd,
+                                      void* stream) {
+    const bool reg = q_tar != nullptr;
+    if (!q || !k || !v || !adj || !dout || !dq || !dk_out || !dv_out || B <= 0 || A <= 0 || A > MAXA || heads <= 0 ||
+        dk <= 0 || dk > MAXD || dv <= 0 || dv > MAXD || ld < (int64_t)heads * (dk > dv ? dk : dv) ||
+        ldo < (int64_t)heads * dv || ldd < (int64_t)heads * (dk > dv ? dk : dv) || (q_tar == nullptr) != (k_tar == nullptr) ||
+        (reg && ld_tar < (int64_t)heads * dk) || (r && !reg))
+        return gm_fail(GM_ERR_INVALID_ARG,
+                       "gm_agent_attention_bwd: bad arguments (A <= 64, dk, dv <= 64; q_tar and k_tar together, r "
+                       "only with them)");
+    const size_t lds = attention_bwd_lds(A, heads, dk, dv, reg);
+    if (lds > 160 * 1024)
+        return gm_fail(GM_ERR_UNSUPPORTED, "gm_agent_attention_bwd: the env's rows need more than 160 KB of LDS");
+    const float scale = 1.0f / sqrtf((float)dk);
+#define GM_ATT_BWD(DD, RR)                                                                                          \
+    do {                                                                                                            \
+        if (!lds_opt_in(k_agent_attention_bwd<DD, RR>, lds))                                                        \
+            return gm_fail(GM_ERR_HIP, "gm_agent_attention_bwd: LDS size refused");                                 \
+        hipLaunchKernelGGL((k_agent_attention_bwd<DD, RR>), dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, v,  \
+                           (long long)ld, adj, A, heads, dk, dv, scale, dout, (long long)ldo, q_tar, k_tar,         \
+                           (long long)ld_tar, r, dq, dk_out, dv_out, (long long)ldd);                               \
+    } while (0)
+    const bool d16 = dk == 16 && dv == 16;
+    if (d16 && reg) GM_ATT_BWD(16, true);
+    else if (d16) GM_ATT_BWD(16, false);
+    else if (reg) GM_ATT_BWD(0, true);
+    else GM_ATT_BWD(0, false);
+#undef GM_ATT_BWD
+    return launched("gm_agent_attention_bwd");
+}
+
+extern "C" int gm_agent_attention_kl(const float* q, const float* k, int64_t ld, const float* q_tar,
+                                     const float* k_tar, int64_t ld_tar, int32_t B, int32_t A, int32_t heads,
+                                     int32_t dk, float* kl_row, void* stream) {
+    if (!q || !k || !q_tar || !k_tar || !kl_row || B <= 0 || A <= 0 || A > MAXA || heads <= 0 || dk <= 0 ||
+        dk > MAXD || ld < (int64_t)heads * dk || ld_tar < (int64_t)heads * dk)
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_agent_attention_kl: bad arguments (A <= 64, dk <= 64)");
+    const size_t lds = (size_t)A * heads * (2 * (size_t)dk + 1) * sizeof(float);
+    if (lds > 160 * 1024)
+        return gm_fail(GM_ERR_UNSUPPORTED, "gm_agent_attention_kl: the env's rows need more than 160 KB of LDS");
+    const float scale = 1.0f / sqrtf((float)dk);
+    if (dk == 16) {
+        if (!lds_opt_in(k_agent_attention_kl<16>, lds)) return gm_fail(GM_ERR_HIP, "gm_agent_attention_kl: LDS size refused");
+        hipLaunchKernelGGL(k_agent_attention_kl<16>, dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, (long long)ld,
+                           q_tar, k_tar, (long long)ld_tar, A, heads, dk, scale, kl_row);
+    } else {
+        if (!lds_opt_in(k_agent_attention_kl<0>, lds)) return gm_fail(GM_ERR_HIP, "gm_agent_attention_kl: LDS size refused");
+        hipLaunchKernelGGL(k_agent_attention_kl<0>, dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, (long long)ld,
+                           q_tar, k_tar, (long long)ld_tar, A, heads, dk, scale, kl_row);
+    }
+    return launched("gm_agent_attention_kl");
 }

@@ -58,6 +58,7 @@ P = importlib.import_module("graph-marl_amd.policy")
 T = importlib.import_module("graph-marl_amd.train")
 TS = importlib.import_module("graph-marl_amd.train_seq")
 AS = importlib.import_module("graph-marl_amd.agent_seq")
+DS = importlib.import_module("graph-marl_amd.dgn_seq")
 RB = importlib.import_module("graph-marl_amd.replaybuffer")
 S = importlib.import_module("graph-marl_amd.simple")
 HEU = importlib.import_module("graph-marl_amd.heuristics")
@@ -486,6 +487,15 @@ def _main(args, rank, world):
                                                           buff.get_agent_sequences(args.mini_batch_size,
                                                                                    args.sequence_length),
                                                           args.gamma, args.tau, args.target_update_steps, iteration)
+                qs, qts = list(q_all), list(qt_all)
+            elif DS.dgn_seq_ok(model, model_tar, netmon, att, aux_model, n_agents):
+                # DGN without NetMon, at every sequence length (1, its default, included: DESIGN 5a): every step's
+                # rows as one batch on the HIP attention kernels (dgn_seq.py)
+                loss, q_all, qt_all = DS.dgn_update_seq(model, model_tar, optimizer, params,
+                                                        buff.get_dgn_sequences(args.mini_batch_size,
+                                                                               args.sequence_length),
+                                                        args.gamma, args.tau, args.target_update_steps, iteration,
+                                                        att_coeff=att, parts=parts)
                 qs, qts = list(q_all), list(qt_all)
             else:
                 batches = list(buff.get_batch(args.mini_batch_size, sequence_length=args.sequence_length,

@@ -259,6 +259,37 @@ class ReplayBuffer:
                              self.next_adj[slots, envs].to(i8) if self.next_adj is not None else None,
                              self._records(self.agent_state, first, env), (slots, env))
 
+    def get_dgn_sequences(self, batch_size, sequence_length):
+        """The transitions get_batch(batch_size, sequence_length) draws (same stream, same indices, for every
+        sequence_length >= 1: a uniform (slot, env) draw at 1, sequences of consecutive slots above), as one
+        dgn_seq.DGNSeqBatch for DGN without NetMon: every step's fields stacked ([L, B, ...], one gather per field),
+        the stored next observations and next adjacency in full (the target model reads them at every step), the
+        adjacencies as int8. DGN carries no state, so none is read."""
+        from .dgn_seq import DGNSeqBatch
+
+        if self.adj is None:
+            raise ValueError("get_dgn_sequences: the buffer stores no agent adjacency")
+        if self.count == 0:
+            raise ValueError("empty replay buffer")
+        Lq = max(1, int(sequence_length))
+        if Lq == 1:
+            f = self.choice(self.count * self.n_env, batch_size)
+            slots, env = (f // self.n_env).unsqueeze(0), f % self.n_env
+        else:
+            if self.count <= Lq:
+                raise ValueError("not enough transitions for the requested sequence length")
+            span = self.count - Lq
+            f = self.choice(self.n_env * span, batch_size)
+            env = f // span
+            first = (self.index % self.count + f % span) % self.count
+            slots = (first.unsqueeze(0) + torch.arange(Lq, device=f.device).unsqueeze(1)) % self.count  # [L, B]
+        envs = env.unsqueeze(0).expand(Lq, -1)
+        i8 = torch.int8
+        return DGNSeqBatch(self._records(self.obs, slots, env), self.obs_dim, self.action[slots, envs].long(),
+                           self.reward[slots, envs].to(torch.float32), self.done[slots, envs],
+                           self.episode_done[slots], self.adj[slots, envs].to(i8),
+                           self._records(self.next_obs, slots, env), self.next_adj[slots, envs].to(i8), (slots, env))
+
     @staticmethod
     def _records(src, slots, env):
         """src[slots, env] as float32 (slots [..., B'] int64 slot indices, env [B'] env indices): one

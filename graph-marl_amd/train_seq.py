@@ -32,7 +32,8 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(no carry-over, global readout, aux loss, DGN, GM_GEMM=f32; DQNR / CommNet without NetMon: agent_seq.py).
+(no carry-over, global readout, aux loss, DGN with NetMon, GM_GEMM=f32; DQNR / CommNet without NetMon:
+agent_seq.py; DGN without NetMon: dgn_seq.py).
 """
 import ctypes as C
 from collections import namedtuple

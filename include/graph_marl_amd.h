@@ -32,6 +32,7 @@
  *   gm_agent_attention               AttModel attention core (DGN)          src/model.py:86-117
  *   gm_agent_comm                    CommNet communication step             src/model.py:780-787
  *   gm_agent_comm_bwd                its transpose (sequence-batched training of CommNet)
+ *   gm_agent_attention_bwd / _kl     transpose of the attention core and the attention regulariser (batched DGN training)
  */
 #ifndef GRAPH_MARL_AMD_H
 #define GRAPH_MARL_AMD_H
@@ -630,6 +631,29 @@ int gm_agent_comm(const float* h, int64_t ldh, const int8_t* adj, int32_t B, int
  * else: GM_ERR_UNSUPPORTED, nothing launched. */
 int gm_agent_comm_bwd(const float* g0, int64_t ld0, const float* g1, int64_t ld1, const int8_t* adj, int32_t B,
                       int32_t A, int32_t H, float* dh, int64_t ldd, void* stream);
+/* Transpose of the gm_agent_attention core (backward of torch autograd through AttModel.forward's matmul /
+ * masked_fill / softmax / matmul + skip, src/model.py:86-117) for B envs: q, k, v rows [B*A][ld] (columns of one
+ * qkv buffer), adj int8 [B][A][A], dout rows [B*A][ldo] the gradient of out. With w, p as above, dP_ij = <dout_i, v_j>
+ * and Ds_i = sum_j p_ij dP_ij: dw_ij = adj_ij ? p_ij (dP_ij - Ds_i) : 0 (masked_fill passes no gradient; a row
+ * without a set entry has uniform p and dw = 0), dq_i = sum_j dw_ij k_j / sqrt(dk), dk_j = sum_i dw_ij q_i / sqrt(dk),
+ * dv_j = sum_i p_ij dout_i + dout_j. Attention regulariser (src/main.py:924-985), optional: q_tar, k_tar rows
+ * [B*A][ld_tar] of the target model (both or neither) and r [B*A] (nullable = 1; only with q_tar) add
+ * r_i (softmax_j(w_i.) - softmax_j(w_tar,i.))_j to dw_i. over ALL j (unmasked softmaxes): the gradient of
+ * sum_i r_i KL(softmax(w_tar,i.) || softmax(w_i.)). dq, dk_out, dv_out: rows [B*A][ldd] (e.g. columns of one
+ * [B*A][heads * (dv + 2 dk)] buffer); they must not alias an input. dk_j and dv_j are summed over i ascending in
+ * fp32 from per-row statistics kept in LDS: no A x A array, no atomics, the same bits on every run. A <= 64,
+ * dk, dv <= 64 (else GM_ERR_INVALID_ARG); an env whose rows need more than 160 KB of LDS: GM_ERR_UNSUPPORTED;
+ * nothing is launched in either case. */
+int gm_agent_attention_bwd(const float* q, const float* k, const float* v, int64_t ld, const int8_t* adj, int32_t B,
+                           int32_t A, int32_t heads, int32_t dk, int32_t dv, const float* dout, int64_t ldo,
+                           const float* q_tar, const float* k_tar, int64_t ld_tar, const float* r, float* dq,
+                           float* dk_out, float* dv_out, int64_t ldd, void* stream);
+/* Forward value of the attention regulariser per source agent (train.attention_kl before its masked mean):
+ * kl_row[b*A + i] = sum_heads sum_j t_ij (log t_ij - log p_ij) with p = softmax_j(w_i.), t = softmax_j(w_tar,i.)
+ * (unmasked), heads and j ascending; both score rows are recomputed on chip from q, k [B*A][ld] and q_tar, k_tar
+ * [B*A][ld_tar]. Limits and refusals as gm_agent_attention_bwd. */
+int gm_agent_attention_kl(const float* q, const float* k, int64_t ld, const float* q_tar, const float* k_tar,
+                          int64_t ld_tar, int32_t B, int32_t A, int32_t heads, int32_t dk, float* kl_row, void* stream);
 
 /* Build provenance: "src=<16 hex digits of the SHA-256 of the csrc sources and headers> arch=<gfx> hipcc=<version>",
  * fixed when the library is linked (tests/test_capi.py checks it against the tree; bench.py reports it). */
