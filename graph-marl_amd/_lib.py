@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GM_LIB") or os.path.join(HERE, "lib", "libgraphmarl_amd.so")
 
 GM_OK = 0
+GM_ERR_UNSUPPORTED = -5
 GM_INFO_FIELDS = 9
 INFO_KEYS = ["looped", "throughput", "dropped", "blocked", "n_delays", "sum_delays", "n_arrived",
              "sum_delays_arrived", "sum_spr"]
@@ -40,7 +41,7 @@ EXPORTS = [
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
-                  "gm_last_kernel"]
+                  "gm_last_kernel", "gm_gemm_kernel_name"]
 
 # Arithmetic form of the fused rollout GEMMs (graph-marl_amd/fused.py): "x3" = split-f16
 # MFMA with fp32 accumulation (default), "f32" = exact fp32 MFMA. GM_GEMM=f32 selects the
@@ -231,6 +232,9 @@ def lib():
         L.gm_gemm_form.restype = C.c_char_p
     if hasattr(L, "gm_last_kernel"):
         L.gm_last_kernel.restype = C.c_char_p
+    if hasattr(L, "gm_gemm_kernel_name"):
+        L.gm_gemm_kernel_name.argtypes = [i32]
+        L.gm_gemm_kernel_name.restype = C.c_char_p
     _lib = L
     return L
 
@@ -269,9 +273,19 @@ def build_info():
 
 
 def last_kernel():
-    """Diagnostic (gm_last_kernel): the kernel this thread's most recent NetMon dispatcher call launched.
+    """Diagnostic (gm_last_kernel): the kernel this thread's most recent NetMon dispatcher or GEMM call launched.
     For the dispatch tests; the product never reads it."""
     return lib().gm_last_kernel().decode()
+
+
+def gemm_kernel_names():
+    """Every kernel name the GEMM entry points of the loaded library can report through gm_last_kernel
+    (gm_gemm_kernel_name; needs no GPU)."""
+    L, out, i = lib(), [], 0
+    while (s := L.gm_gemm_kernel_name(i)) is not None:
+        out.append(s.decode())
+        i += 1
+    return out
 
 
 def check(rc):

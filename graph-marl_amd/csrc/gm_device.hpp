@@ -8,6 +8,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// gm_last_kernel (graph_marl_amd_tuning.h): the dispatchers of gm_netmon.hip and gm_gemm.hip name the kernel
+// they launch through this setter (one thread-local pointer, defined in gm_netmon.hip). `name` must outlive
+// the call: a string literal or a string with static storage.
+void gm_set_last_kernel(const char* name);
+
 namespace gm {
 
 constexpr int WAVE = 64;

@@ -50,10 +50,13 @@
 #error "GM_DIAG must be 0 or 30"
 #endif
 #include <string>
+#include <vector>
 
 #include "../../include/graph_marl_amd.h"
+#include "../../include/graph_marl_amd_tuning.h"
 #include "gm_amax.hpp"
 #include "gm_act.hpp"
+#include "gm_device.hpp"
 
 int gm_fail(int code, const std::string& msg);
 
@@ -2263,20 +2266,62 @@ int g_mfma16 = 2;
 // 128x128 (4 waves), 2 k_gemm3g 128x256 (8 waves)
 int g_dgrad = -1;
 
+// Kernel names for gm_last_kernel / gm_gemm_kernel_name (graph_marl_amd_tuning.h). launch and launch_g below are
+// the only launchers of k_gemm, k_gemm3 and k_gemm3g: each names its kernel from its own template parameters
+// through KName<...>::name, a static data member whose initialiser (run when the library loads, for exactly the
+// instantiations the launchers were compiled for) also enters the name in the list gm_gemm_kernel_name walks.
+// One host store per call, nothing on the device.
+std::vector<const char*>& kernel_names() {
+    static std::vector<const char*> v;
+    return v;
+}
+const char* register_kernel_name(const std::string& name) {
+    const char* p = (new std::string(name))->c_str();  // lives as long as the library
+    kernel_names().push_back(p);
+    return p;
+}
+const char* amode_name(int a) {
+    return a == GM_A_DENSE ? "DENSE" : a == GM_A_AGGREGATE ? "AGGREGATE" : a == GM_A_READOUT ? "READOUT" : "ROUTING_ENC";
+}
+const char* epi_name(int e) {
+    return e == EPI_BIAS ? "BIAS" : e == EPI_LSTM ? "LSTM" : e == EPI_HEAD ? "HEAD" : e == EPI_DGRAD ? "DGRAD" : "CHAIN";
+}
+// FAM 0: k_gemm<.., BK, ..>, 1: k_gemm3<.., BK, ..> (P5 = BK, AX = MF = 0), 2: k_gemm3g<.., STAGES, .., AX, MF>
+template <int FAM, int WGM, int WGN, int TM, int TN, int P5, int AMODE, int EPI, int OCC, int AX, int MF>
+struct KName {
+    static const char* const name;
+};
+template <int FAM, int WGM, int WGN, int TM, int TN, int P5, int AMODE, int EPI, int OCC, int AX, int MF>
+const char* const KName<FAM, WGM, WGN, TM, TN, P5, AMODE, EPI, OCC, AX, MF>::name = register_kernel_name(
+    std::string(FAM == 0 ? "k_gemm<" : FAM == 1 ? "k_gemm3<" : "k_gemm3g<") + std::to_string(WGM) + "," +
+    std::to_string(WGN) + "," + std::to_string(TM) + "," + std::to_string(TN) + (FAM == 2 ? ",S" : ",BK") +
+    std::to_string(P5) + "," + amode_name(AMODE) + "," + epi_name(EPI) + ",occ" + std::to_string(OCC) +
+    (FAM == 2 ? ",AX" + std::to_string(AX) + ",MF" + std::to_string(MF) : std::string()) + ">");
+// the weight-gradient forms of wgrad_launch, entered explicitly
+const char* const WG_KMAJOR = register_kernel_name("k_gemm3_kmajor");
+const char* const WG_TR128[2][2] = {
+    {register_kernel_name("k_wgrad_tr<128,0>"), register_kernel_name("k_wgrad_tr<128,0>/xcd")},
+    {register_kernel_name("k_wgrad_tr<128,1>"), register_kernel_name("k_wgrad_tr<128,1>/xcd")}};
+const char* const WG_TR256[2] = {register_kernel_name("k_wgrad_tr<256,0>"), register_kernel_name("k_wgrad_tr<256,0>/xcd")};
+
 template <int WGM, int WGN, int TM, int TN, int STAGES, int AMODE, int EPI, int OCC, int AX = 0>
 int launch_g(const ASrc& a0, const ASrc& a1, const float* w, long long ldw, unsigned wbytes, int M, int N, int K,
              const Epi& ep, hipStream_t st, const float* wscale_inv, int mf = -1) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     const int T = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    if constexpr (AMODE == GM_A_ROUTING_ENC)  // 16x16x32 only
+    if constexpr (AMODE == GM_A_ROUTING_ENC) {  // 16x16x32 only
+        gm_set_last_kernel(KName<2, WGM, WGN, TM, TN, STAGES, AMODE, EPI, OCC, AX, 1>::name);
         hipLaunchKernelGGL((k_gemm3g<WGM, WGN, TM, TN, STAGES, AMODE, EPI, OCC, AX, 1>), dim3(T), dim3(WGM * WGN * 64), 0,
                            st, a0, a1, reinterpret_cast<const _Float16*>(w), ldw, wbytes, M, N, K, ep, wscale_inv);
-    else if (mf < 0 ? g_mfma16 : mf)
+    } else if (mf < 0 ? g_mfma16 : mf) {
+        gm_set_last_kernel(KName<2, WGM, WGN, TM, TN, STAGES, AMODE, EPI, OCC, AX, 1>::name);
         hipLaunchKernelGGL((k_gemm3g<WGM, WGN, TM, TN, STAGES, AMODE, EPI, OCC, AX, 1>), dim3(T), dim3(WGM * WGN * 64), 0,
                            st, a0, a1, reinterpret_cast<const _Float16*>(w), ldw, wbytes, M, N, K, ep, wscale_inv);
-    else
+    } else {
+        gm_set_last_kernel(KName<2, WGM, WGN, TM, TN, STAGES, AMODE, EPI, OCC, AX, 0>::name);
         hipLaunchKernelGGL((k_gemm3g<WGM, WGN, TM, TN, STAGES, AMODE, EPI, OCC, AX, 0>), dim3(T), dim3(WGM * WGN * 64), 0,
                            st, a0, a1, reinterpret_cast<const _Float16*>(w), ldw, wbytes, M, N, K, ep, wscale_inv);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gm_fail(GM_ERR_HIP, std::string("gm_gemm launch: ") + hipGetErrorString(e));
     return GM_OK;
@@ -2287,6 +2332,7 @@ int launch(const ASrc& a0, const ASrc& a1, const float* w, long long ldw, unsign
            const Epi& ep, hipStream_t st, const float* wscale_inv = nullptr) {
     using C = Cfg<WGM, WGN, TM, TN, BK_>;
     const int T = ((M + C::BM - 1) / C::BM) * ((N + C::BN - 1) / C::BN);
+    gm_set_last_kernel(KName<X3 ? 1 : 0, WGM, WGN, TM, TN, BK_, AMODE, EPI, OCC, 0, 0>::name);
     if constexpr (X3)
         hipLaunchKernelGGL((k_gemm3<WGM, WGN, TM, TN, BK_, AMODE, EPI, OCC>), dim3(T), dim3(C::THREADS), 0, st, a0, a1,
                            reinterpret_cast<const _Float16*>(w), ldw, wbytes, M, N, K, ep, wscale_inv);
@@ -3353,6 +3399,7 @@ static int wgrad_launch(const float* a, int64_t lda, const gm_wgrad_src& s1, int
                                                                "transposed-read forms and n1 % 128 == 0");
     if (g_wgrad == 0) {
         const int T = ((m + 127) / 128) * ((n + 127) / 128);
+        gm_set_last_kernel(WG_KMAJOR);
         hipLaunchKernelGGL(k_gemm3_kmajor, dim3(T, S), dim3(256), 0, (hipStream_t)stream, a, (long long)lda, s1.p,
                            (long long)s1.ld, m, n, k, kchunk, sa, s1.scale, c, (long long)ldc, (long long)m * ldc);
     } else {
@@ -3366,18 +3413,22 @@ static int wgrad_launch(const float* a, int64_t lda, const gm_wgrad_src& s1, int
         const int T128 = ((m + 127) / 128) * ((n + 127) / 128);
         const int xcd = g_wgrad_xcd && (T128 * S) % 8 == 0;
         if (g_wgrad == 3) {  // 16x16x32 MFMA
+            gm_set_last_kernel(WG_TR128[1][xcd]);
             hipLaunchKernelGGL((k_wgrad_tr<128, 1>), dim3(T128, S), dim3(256), 0, (hipStream_t)stream, a,
                                (long long)lda, (unsigned)ab, w1, w2, n1, m, n, k, kchunk, sa, c, (long long)ldc,
                                (long long)m * ldc, xcd);
         } else if (g_wgrad != 2) {  // 128 x 128 tiles at 2 blocks/CU: 8-24 % faster than 128 x 256 at 1 block/CU
+            gm_set_last_kernel(WG_TR128[0][xcd]);
             hipLaunchKernelGGL(k_wgrad_tr<128>, dim3(T128, S), dim3(256), 0, (hipStream_t)stream, a, (long long)lda,
                                (unsigned)ab, w1, w2, n1, m, n, k, kchunk, sa, c, (long long)ldc, (long long)m * ldc,
                                xcd);
         } else {
             const int T = ((m + 127) / 128) * ((n + 255) / 256);
+            const int xcd256 = g_wgrad_xcd && (T * S) % 8 == 0;
+            gm_set_last_kernel(WG_TR256[xcd256]);
             hipLaunchKernelGGL(k_wgrad_tr<256>, dim3(T, S), dim3(256), 0, (hipStream_t)stream, a, (long long)lda,
                                (unsigned)ab, w1, w2, n1, m, n, k, kchunk, sa, c, (long long)ldc, (long long)m * ldc,
-                               (int)(g_wgrad_xcd && (T * S) % 8 == 0));
+                               xcd256);
         }
     }
     hipError_t e = hipGetLastError();
@@ -3447,6 +3498,11 @@ extern "C" int gm_gemm_set_mfma(int32_t shape) {
 extern "C" const char* gm_gemm_form(void) { return "x3=lo" GM_STR(GM_LO_E) " diag=" GM_STR(GM_DIAG); }
 #undef GM_STR
 #undef GM_STR2
+
+extern "C" const char* gm_gemm_kernel_name(int32_t i) {
+    const std::vector<const char*>& v = kernel_names();
+    return i >= 0 && (size_t)i < v.size() ? v[(size_t)i] : nullptr;
+}
 
 extern "C" int gm_gemm_set_tile(int32_t tile) {
     if (tile < -1 || tile > 14) return gm_fail(GM_ERR_INVALID_ARG, "gm_gemm_set_tile: tile in [-1, 14]");

@@ -18,6 +18,7 @@
 #include "../../include/graph_marl_amd_tuning.h"
 #include "gm_amax.hpp"
 #include "gm_act.hpp"
+#include "gm_device.hpp"
 
 int gm_fail(int code, const std::string& msg);
 
@@ -468,9 +469,11 @@ static int vec_width(int H, long long stride, const void* p) {
 }
 
 // gm_last_kernel (diagnostics, graph_marl_amd_tuning.h): every launch site of the dispatchers below names its
-// kernel first: one host store per call
+// kernel first: one host store per call. The state sits behind gm_set_last_kernel (gm_device.hpp), which the
+// GEMM launchers of gm_gemm.hip call too.
 static thread_local const char* g_last_kernel = "";
-#define GM_RAN(NAME) (g_last_kernel = (NAME))
+void gm_set_last_kernel(const char* name) { g_last_kernel = name; }
+#define GM_RAN(NAME) gm_set_last_kernel(NAME)
 extern "C" const char* gm_last_kernel(void) { return g_last_kernel; }
 
 #define GM_VLAUNCH(KER, V, GRID, ...)                                                                  \

@@ -284,9 +284,12 @@ def _wgrad2(gy, srcs, sa):
     lib = FU._setup()
     part = torch.empty(splits, o, N, device=gy.device)
     spec = [L.WgradSrc(x.data_ptr(), x.stride(0), sb.data_ptr(), per, sh, x.shape[0]) for x, _, sb, per, sh in srcs]
-    L.check(lib.gm_gemm_x3_wgrad2(gy.data_ptr(), o, C.byref(spec[0]), Ns[0],
-                                  C.byref(spec[1]) if len(spec) > 1 else None, Ns[1] if len(spec) > 1 else 0, o, Mb,
-                                  kchunk, sa.data_ptr(), part.data_ptr(), N, L.stream_ptr()))
+    rc = lib.gm_gemm_x3_wgrad2(gy.data_ptr(), o, C.byref(spec[0]), Ns[0],
+                               C.byref(spec[1]) if len(spec) > 1 else None, Ns[1] if len(spec) > 1 else 0, o, Mb,
+                               kchunk, sa.data_ptr(), part.data_ptr(), N, L.stream_ptr())
+    if rc == L.GM_ERR_UNSUPPORTED:  # the selected kernel form (gm_gemm_set_wgrad 0 / 2) takes one plain source only
+        return None
+    L.check(rc)
     tot = part.sum(0)
     out, c0 = [], 0
     for (_, k, _, _, _), n in zip(srcs, Ns):

@@ -34,11 +34,23 @@ int gm_gemm_set_dgrad(int32_t form);
  * with the A operand's low piece scaled by 2^12 in every kernel (the only form since round 5);
  * diag = 0 for the product build, 30 for the k-step stamp build (tools/stamp_bench.py). */
 const char* gm_gemm_form(void);
-/* Diagnostic: the kernel the most recent call on this thread of gm_netmon_readout[_ld], gm_netmon_readout_bwd[_sym],
- * gm_mp_aggregate[_rows|_bwd], gm_lstm_cell_bwd or gm_qhead_bwd launched, as a string literal such as
- * "k_readout_bwd_cs<2>/S=8" ("" before the first such call). One host store per call; the tests of the
- * dispatch thresholds read it (tests/test_netmon_paths_gpu.py), the product never does. */
+/* Diagnostic: the kernel the most recent call on this thread of a dispatching entry point launched ("" before
+ * the first such call). NetMon: gm_netmon_readout[_ld], gm_netmon_readout_bwd[_sym], gm_mp_aggregate[_rows|_bwd],
+ * gm_lstm_cell_bwd and gm_qhead_bwd report a string literal such as "k_readout_bwd_cs<2>/S=8". GEMMs:
+ * gm_gemm_f32 (gm_linear_f32), gm_gemm_x3, gm_gemm_x3_dgrad, gm_gemm_x3_head, gm_encoder_x3 and
+ * gm_gemm_x3_wgrad[2] report the instantiation with its template parameters, e.g.
+ * "k_gemm<2,2,2,2,BK16,DENSE,BIAS,occ2>", "k_gemm3<4,1,1,4,BK16,AGGREGATE,LSTM,occ2>" (wave grid WGM x WGN,
+ * 32x32 tiles per wave TM x TN, k tile, A source, epilogue, blocks per CU),
+ * "k_gemm3g<4,2,1,4,S3,DENSE,BIAS,occ1,AX1,MF1>" (.., stages, .., AX 0 plain / 1 publishes max|A| / 2 scaled A,
+ * MF 0 32x32x16 / 1 16x16x32 MFMA), "k_gemm3_kmajor", "k_wgrad_tr<128,0>" (tile width, MFMA form) with "/xcd"
+ * appended when the k chunks are grouped per XCD. One thread-local state for both families, one host store
+ * per call, nothing on the device; the tests of the dispatch thresholds read it
+ * (tests/test_netmon_paths_gpu.py, tests/test_gemm_paths_gpu.py), the product never does. */
 const char* gm_last_kernel(void);
+/* The i-th kernel name the GEMM entry points of this build can report through gm_last_kernel, NULL past the
+ * end: exactly the instantiations the two GEMM launchers were compiled for, plus the weight-gradient forms.
+ * Filled when the library loads; needs no GPU. tests/test_gemm_paths_gpu.py requires a case for every name. */
+const char* gm_gemm_kernel_name(int32_t i);
 
 #ifdef __cplusplus
 }
