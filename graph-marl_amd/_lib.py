@@ -273,7 +273,8 @@ def build_info():
 
 
 def last_kernel():
-    """Diagnostic (gm_last_kernel): the kernel this thread's most recent NetMon dispatcher or GEMM call launched.
+    """Diagnostic (gm_last_kernel): the kernel this thread's most recent NetMon dispatcher, agent-kernel launcher
+    (gm_agent_*) or GEMM call launched.
     For the dispatch tests; the product never reads it."""
     return lib().gm_last_kernel().decode()
 

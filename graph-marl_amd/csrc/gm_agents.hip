@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/graph_marl_amd.h"
+#include "gm_device.hpp"
 
 int gm_fail(int code, const std::string& msg);
 
@@ -511,6 +512,13 @@ int launched(const char* what) {
 
 }  // namespace
 
+// Dynamic LDS above 64 KB has to be asked for per kernel before the launch; nothing to do at or below it.
+template <typename K>
+static bool lds_opt_in(K kern, size_t lds) {
+    return lds <= 64 * 1024 ||
+           hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+}
+
 extern "C" int gm_agent_attention(const float* q, const float* k, const float* v, int64_t ld, const int8_t* adj,
                                   int32_t B, int32_t A, int32_t heads, int32_t dk, int32_t dv, float* out,
                                   int64_t ldo, float* att_weights, void* stream) {
@@ -520,12 +528,17 @@ extern "C" int gm_agent_attention(const float* q, const float* k, const float* v
     const size_t lds = (size_t)A * heads * (dk + dv) * sizeof(float);
     if (lds > 160 * 1024) return gm_fail(GM_ERR_UNSUPPORTED, "gm_agent_attention: A * heads * (dk + dv) too large");
     const float scale = 1.0f / sqrtf((float)dk);
-    if (dk == 16 && dv == 16)
+    if (dk == 16 && dv == 16) {
+        if (!lds_opt_in(k_agent_attention<16>, lds)) return gm_fail(GM_ERR_HIP, "gm_agent_attention: LDS size refused");
+        gm_set_last_kernel("k_agent_attention<16>");
         hipLaunchKernelGGL(k_agent_attention<16>, dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, v,
                            (long long)ld, adj, A, heads, dk, dv, scale, out, (long long)ldo, att_weights);
-    else
+    } else {
+        if (!lds_opt_in(k_agent_attention<0>, lds)) return gm_fail(GM_ERR_HIP, "gm_agent_attention: LDS size refused");
+        gm_set_last_kernel("k_agent_attention<0>");
         hipLaunchKernelGGL(k_agent_attention<0>, dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, v,
                            (long long)ld, adj, A, heads, dk, dv, scale, out, (long long)ldo, att_weights);
+    }
     return launched("gm_agent_attention");
 }
 
@@ -533,6 +546,7 @@ extern "C" int gm_agent_comm(const float* h, int64_t ldh, const int8_t* adj, int
                              float* out, int64_t ldo, void* stream) {
     if (!h || !adj || !out || B <= 0 || A <= 0 || A > MAXA || H <= 0 || ldh < H || ldo < H || h == out)
         return gm_fail(GM_ERR_INVALID_ARG, "gm_agent_comm: bad arguments (A <= 64, out must not alias h)");
+    gm_set_last_kernel("k_agent_comm");
     hipLaunchKernelGGL(k_agent_comm, dim3(B), dim3(256), 0, (hipStream_t)stream, h, (long long)ldh, adj, A, H, out,
                        (long long)ldo);
     return launched("gm_agent_comm");
@@ -547,12 +561,15 @@ extern "C" int gm_agent_comm_bwd(const float* g0, int64_t ld0, const float* g1, 
         return gm_fail(GM_ERR_UNSUPPORTED, "gm_agent_comm_bwd: A <= 64 and H <= 1024 only");
     auto a16 = [](const void* p, int64_t ld) { return !p || ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0); };
     const dim3 grid((unsigned)B, (unsigned)((H + COMM_CH - 1) / COMM_CH));
-    if (H % 4 == 0 && a16(g0, ld0) && a16(g1, ld1) && a16(dh, ldd))
+    if (H % 4 == 0 && a16(g0, ld0) && a16(g1, ld1) && a16(dh, ldd)) {
+        gm_set_last_kernel("k_agent_comm_bwd<4>");
         hipLaunchKernelGGL(k_agent_comm_bwd<4>, grid, dim3(256), 0, (hipStream_t)stream, g0, (long long)ld0, g1,
                            (long long)ld1, adj, A, H, dh, (long long)ldd);
-    else
+    } else {
+        gm_set_last_kernel("k_agent_comm_bwd<1>");
         hipLaunchKernelGGL(k_agent_comm_bwd<1>, grid, dim3(256), 0, (hipStream_t)stream, g0, (long long)ld0, g1,
                            (long long)ld1, adj, A, H, dh, (long long)ldd);
+    }
     return launched("gm_agent_comm_bwd");
 }
 
@@ -560,12 +577,6 @@ extern "C" int gm_agent_comm_bwd(const float* g0, int64_t ld0, const float* g1, 
 static size_t attention_bwd_lds(int A, int heads, int dk, int dv, bool reg) {
     const size_t fl = (size_t)A * heads * ((reg ? 2 : 1) * (size_t)dk + (size_t)dv + (reg ? 8 : 3));
     return fl * sizeof(float) + (((size_t)A * A + 15) & ~(size_t)15);
-}
-
-template <typename K>
-static bool lds_opt_in(K kern, size_t lds) {
-    return lds <= 64 * 1024 ||
-           hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
 extern "C" int gm_agent_attention_bwd(const float* q, const float* k, const float* v, int64_t ld, const int8_t* adj,
@@ -589,6 +600,7 @@ extern "C" int gm_agent_attention_bwd(const float* q, const float* k, const floa
     do {                                                                                                            \
         if (!lds_opt_in(k_agent_attention_bwd<DD, RR>, lds))                                                        \
             return gm_fail(GM_ERR_HIP, "gm_agent_attention_bwd: LDS size refused");                                 \
+        gm_set_last_kernel((RR) ? "k_agent_attention_bwd<" #DD ",reg>" : "k_agent_attention_bwd<" #DD ",plain>");   \
         hipLaunchKernelGGL((k_agent_attention_bwd<DD, RR>), dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, v,  \
                            (long long)ld, adj, A, heads, dk, dv, scale, dout, (long long)ldo, q_tar, k_tar,         \
                            (long long)ld_tar, r, dq, dk_out, dv_out, (long long)ldd);                               \
@@ -614,10 +626,12 @@ extern "C" int gm_agent_attention_kl(const float* q, const float* k, int64_t ld,
     const float scale = 1.0f / sqrtf((float)dk);
     if (dk == 16) {
         if (!lds_opt_in(k_agent_attention_kl<16>, lds)) return gm_fail(GM_ERR_HIP, "gm_agent_attention_kl: LDS size refused");
+        gm_set_last_kernel("k_agent_attention_kl<16>");
         hipLaunchKernelGGL(k_agent_attention_kl<16>, dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, (long long)ld,
                            q_tar, k_tar, (long long)ld_tar, A, heads, dk, scale, kl_row);
     } else {
         if (!lds_opt_in(k_agent_attention_kl<0>, lds)) return gm_fail(GM_ERR_HIP, "gm_agent_attention_kl: LDS size refused");
+        gm_set_last_kernel("k_agent_attention_kl<0>");
         hipLaunchKernelGGL(k_agent_attention_kl<0>, dim3(B), dim3(256), lds, (hipStream_t)stream, q, k, (long long)ld,
                            q_tar, k_tar, (long long)ld_tar, A, heads, dk, scale, kl_row);
     }
