@@ -964,6 +964,99 @@ extern "C" int gm_netmon_readout_bwd_sym(const float* dout, int64_t stride, cons
     return readout_bwd(dout, stride, nbr, nullptr, G, N, N, deg, H, dhf, dhp, true, stream);
 }
 
+// Global-mean readout (--netmon-global, src/model.py:458-469, 624-627): the mean of h over a graph's nodes,
+// broadcast to the graph's output rows. A block owns gpb whole graphs; a thread owns one V-float column chunk of
+// one graph (lanes run along H, so every row access is contiguous), sums the N node rows in ascending order in
+// fp32 (the value does not depend on the launch shape) and stores the mean into the graph's R rows. No atomics.
+template <int V>
+__global__ __launch_bounds__(256) void k_global_rows(const float* __restrict__ state, long long lds, int G, int N,
+                                                     int HV, int R, int gpb, float* __restrict__ out,
+                                                     long long ldo) {
+    const float inv = 1.0f / (float)N;
+    for (int i = threadIdx.x; i < gpb * HV; i += blockDim.x) {
+        const int gl = i / HV, c = (i - gl * HV) * V;
+        const long long g = (long long)blockIdx.x * gpb + gl;
+        if (g >= G) break;  // gl ascends with i
+        const float* s = state + g * N * lds + c;
+        Vec<V> acc = zerov<V>();
+#pragma unroll 4
+        for (int n = 0; n < N; n++) {
+            const Vec<V> x = ldv<V>(s + n * lds);
+#pragma unroll
+            for (int k = 0; k < V; k++) acc.v[k] += x.v[k];
+        }
+#pragma unroll
+        for (int k = 0; k < V; k++) acc.v[k] *= inv;
+        float* o = out + g * R * ldo + c;
+        for (int r = 0; r < R; r++) stv<V>(o + r * ldo, acc);
+    }
+}
+
+// Its transpose, accumulated: dh[node n of graph g] += (1/N) * (sum over the graph's rows r, ascending, of d_rows).
+// The same ownership (one thread per graph and column chunk), so plain loads and stores suffice.
+template <int V>
+__global__ __launch_bounds__(256) void k_global_bwd(const float* __restrict__ d, long long ldd, int G, int N, int HV,
+                                                    int R, int gpb, float* __restrict__ dh, long long ldh) {
+    const float inv = 1.0f / (float)N;
+    for (int i = threadIdx.x; i < gpb * HV; i += blockDim.x) {
+        const int gl = i / HV, c = (i - gl * HV) * V;
+        const long long g = (long long)blockIdx.x * gpb + gl;
+        if (g >= G) break;
+        const float* s = d + g * R * ldd + c;
+        Vec<V> acc = zerov<V>();
+#pragma unroll 4
+        for (int r = 0; r < R; r++) {
+            const Vec<V> x = ldv<V>(s + r * ldd);
+#pragma unroll
+            for (int k = 0; k < V; k++) acc.v[k] += x.v[k];
+        }
+#pragma unroll
+        for (int k = 0; k < V; k++) acc.v[k] *= inv;
+        float* o = dh + g * N * ldh + c;
+        for (int n = 0; n < N; n++) {
+            Vec<V> x = ldv<V>(o + n * ldh);
+#pragma unroll
+            for (int k = 0; k < V; k++) x.v[k] += acc.v[k];
+            stv<V>(o + n * ldh, x);
+        }
+    }
+}
+
+static bool global_args_ok(const void* a, int64_t lda, int32_t G, int32_t N, int32_t H, int32_t R, const void* b,
+                           int64_t ldb) {
+    return a && b && G > 0 && N > 0 && N <= 128 && R > 0 && H > 0 && H % 32 == 0 && H <= 1024 && lda >= H &&
+           ldb >= H && (reinterpret_cast<uintptr_t>(a) & 3) == 0 && (reinterpret_cast<uintptr_t>(b) & 3) == 0;
+}
+
+// graphs per block: 256 threads' worth of column chunks, one graph when a graph has that many
+static int global_gpb(int HV) { return HV >= 256 ? 1 : 256 / HV; }
+
+extern "C" int gm_netmon_global_rows(const float* state, int64_t ld_state, int32_t G, int32_t N, int32_t H,
+                                     int32_t R, float* out, int64_t ld_out, void* stream) {
+    if (!global_args_ok(state, ld_state, G, N, H, R, out, ld_out))
+        return gm_fail(GM_ERR_INVALID_ARG,
+                       "gm_netmon_global_rows: bad arguments (hidden % 32 == 0, hidden <= 1024, n_nodes <= 128, ld >= hidden)");
+    const int v0 = vec_width(H, ld_state, state), v1 = vec_width(H, ld_out, out);
+    const int V = v0 < v1 ? v0 : v1;  // scalar dword stores when the output base or stride is not 8 / 16-byte aligned
+    const int HV = H / V, gpb = global_gpb(HV);
+    GM_VLAUNCH(k_global_rows, V, dim3(nblocks(G, gpb)), state, (long long)ld_state, (int)G, (int)N, HV, (int)R, gpb, out,
+               (long long)ld_out);
+    return launched();
+}
+
+extern "C" int gm_netmon_global_bwd(const float* d_rows, int64_t ld_d, int32_t G, int32_t N, int32_t H, int32_t R,
+                                    float* dh, int64_t ld_dh, void* stream) {
+    if (!global_args_ok(d_rows, ld_d, G, N, H, R, dh, ld_dh))
+        return gm_fail(GM_ERR_INVALID_ARG,
+                       "gm_netmon_global_bwd: bad arguments (hidden % 32 == 0, hidden <= 1024, n_nodes <= 128, ld >= hidden)");
+    const int v0 = vec_width(H, ld_d, d_rows), v1 = vec_width(H, ld_dh, dh);
+    const int V = v0 < v1 ? v0 : v1;
+    const int HV = H / V, gpb = global_gpb(HV);
+    GM_VLAUNCH(k_global_bwd, V, dim3(nblocks(G, gpb)), d_rows, (long long)ld_d, (int)G, (int)N, HV, (int)R, gpb, dh,
+               (long long)ld_dh);
+    return launched();
+}
+
 extern "C" int gm_lstm_pointwise(const float* gates, const float* c, int32_t m, int32_t H, float* h1, float* c1,
                                  float* act, void* stream) {
     if (!gates || !c || !h1 || !c1 || m <= 0 || H <= 0) return gm_fail(GM_ERR_INVALID_ARG, "gm_lstm_pointwise: bad args");

@@ -10,6 +10,9 @@ last update (readout's neighbour features, src/model.py:510-519).
 DQN Q (src/model.py:187-203) on the joint observation without materialising it:
   h1 = leaky(W1 @ [readout(h_final, h_prev, nbr, agent_node) | env_obs] + b1)
 so the NetMon readout + agent gather (src/model.py:582-631) happen in the GEMM's A load.
+With the global mean (output_global_hidden, src/model.py:458-469, 624-627) the dense source is
+[env_obs | mean of h over the graph] (gm_netmon_global_rows writes the mean behind the env
+observation) and W1's columns are packed [h | nbr x 3 | env | global].
 Weights are packed once per parameter version (LSTM gate interleave, W1 column order,
 and for the split-f16 form (L.GEMM_MODE == "x3", gm_gemm_x3) the hi/lo f16 split).
 """
@@ -298,24 +301,45 @@ def fold_env_weight(we, n):
     return out.to(we.dtype)
 
 
-def pack_dqn_first(lin, obs_dim, fold_n=None):
+def global_first_cols(w, od, H, order):
+    """Columns of a first DQN layer weight (or of its gradient) [n, od + 5H] in the reference order [env | h |
+    global | nbr x 3] (src/model.py:458-469), reordered for the two GEMM sources of the global readout:
+    "env_global": [h | nbr x 3 | env | global] (READOUT source + dense [env obs | global] rows, the rollout);
+    "global_env": [h | nbr x 3 | global | env] (dense 5H graph rows + env obs, the sequence-batched update)."""
+    env, h, g, nb = w[:, :od], w[:, od:od + H], w[:, od + H:od + 2 * H], w[:, od + 2 * H:]
+    return torch.cat([h, nb, env, g] if order == "env_global" else [h, nb, g, env], 1)
+
+
+def pack_dqn_first(lin, obs_dim, fold_n=None, global_h=None, order="env_global"):
     """W1 columns reordered to [graph part | env obs part] to match A = [readout | env obs];
-    fold_n = N: env part folded to the 6N+8 columns of the GEMM-ready obs copy."""
-    if not hasattr(lin, "_packed_first"):
-        lin._packed_first = Packed()
+    fold_n = N: env part folded to the 6N+8 columns of the GEMM-ready obs copy. global_h = H: the graph part
+    holds the global mean ([h | global | nbr x 3]); columns in global_first_cols' `order`, one cached pack per
+    order (the target network's update runs both)."""
+    if global_h is None:
+        if not hasattr(lin, "_packed_first"):
+            lin._packed_first = Packed()
+        cache = lin._packed_first
+    else:
+        assert fold_n is None, "the GEMM-ready env copy has no room for the global columns"
+        if not hasattr(lin, "_packed_first_g"):
+            lin._packed_first_g = {"env_global": Packed(), "global_env": Packed()}
+        cache = lin._packed_first_g[order]
 
     def build():
         with torch.no_grad():
             we = lin.weight[:, :obs_dim]
             if fold_n is not None:
                 we = fold_env_weight(we, fold_n)
-            w = torch.cat([lin.weight[:, obs_dim:], we], 1).contiguous()
+            if global_h is None:
+                w = torch.cat([lin.weight[:, obs_dim:], we], 1).contiguous()
+            else:
+                w = global_first_cols(lin.weight, obs_dim, global_h, order).contiguous()
             wp, ldw = _pad_cols(w)
             n = lin.out_features
             x3 = X3(wp, ldw, n, w.shape[1]) if use_x3(n) else None
             return wp, ldw, lin.bias.contiguous(), x3
 
-    return lin._packed_first.get(_key(lin.weight, lin.bias) + (obs_dim, fold_n, L.GEMM_MODE), build)
+    return cache.get(_key(lin.weight, lin.bias) + (obs_dim, fold_n, L.GEMM_MODE), build)
 
 
 def pack_x3(lin):
@@ -473,9 +497,18 @@ def _cell_step(netmon, cell, x_src, h_ptr, ldh, c_ptr, ldc, S, M, tag_kind):
 
 def fused_ok(netmon):
     """The fused no-grad NetMon step covers lstm / lnlstm / gru with state carry-over and the
-    neighbour readout (the reference's NetMonWrapper configuration on routing graphs)."""
+    neighbour readout (the reference's NetMonWrapper configuration on routing graphs), with or without the
+    global mean (output_global_hidden: gm_netmon_global_rows, H <= 1024)."""
     return (netmon.rnn_type in ("lstm", "lnlstm", "gru") and netmon.rnn_carryover and netmon.output_neighbor_hidden
-            and not netmon.output_global_hidden and netmon.hidden_features % 32 == 0)
+            and netmon.hidden_features % 32 == 0
+            and (not netmon.output_global_hidden or netmon.hidden_features <= 1024))
+
+
+def global_rows(state, ld_state, G, N, H, rows, out, ld_out):
+    """The mean of h over each graph's N nodes into H columns of the graph's `rows` output rows
+    (gm_netmon_global_rows); state / out: device pointers of the first h column / the first column written."""
+    with L.timed(f"gm_netmon_global_rows:{G * rows}x{H}"):
+        L.check(L.lib().gm_netmon_global_rows(state, ld_state, G, N, H, rows, out, ld_out, L.stream_ptr()))
 
 
 @torch.no_grad()
@@ -550,20 +583,25 @@ def netmon_step(netmon, node_obs, nbr, state, out=None, last_out=None):
 
 
 @torch.no_grad()
-def dqn_q(dqn, env_obs, obs_dim, state, h_prev, nbr, agent_node, scratch, hidden=None, obs_gemm=None):
+def dqn_q(dqn, env_obs, obs_dim, state, h_prev, nbr, agent_node, scratch, hidden=None, obs_gemm=None,
+          global_cols=False):
     """Q [B*A, actions] of the DQN on [env obs | NetMon readout] with the readout gathered
     inside the first GEMM. env_obs: [B, A, stride] (first obs_dim columns used); state rows
     [h | ...] of width state.shape[-1] (hidden H: default half the width, the LSTM layout).
     obs_gemm: the env's GEMM-ready copy [B, A, 6N+8] (Routing.enable_gemm_obs): read instead of
-    env_obs with the folded weights (K two columns shorter: whole k tiles at N = 20)."""
+    env_obs with the folded weights (K two columns shorter: whole k tiles at N = 20).
+    global_cols: NetMon's output_global_hidden; the H columns after the env observation in env_obs hold the
+    graph's mean of h (global_rows), so the dense source is [env obs | global] and obs_gemm is not read."""
     B, A, stride = env_obs.shape
     N = nbr.shape[1]
     H = hidden or state.shape[-1] // 2
     M = B * A
     lin0 = dqn.encoder.linear_layers[0]
-    fold = obs_gemm is not None and obs_dim == 6 * N + 10
-    wp, ldw, b, x3 = pack_dqn_first(lin0, obs_dim, N if fold else None)
-    if fold:
+    fold = obs_gemm is not None and obs_dim == 6 * N + 10 and not global_cols
+    wp, ldw, b, x3 = pack_dqn_first(lin0, obs_dim, N if fold else None, H if global_cols else None)
+    if global_cols:
+        src, ks = dense(env_obs.data_ptr(), stride, obs_dim + H), obs_dim + H
+    elif fold:
         src, ks = dense(obs_gemm.data_ptr(), obs_gemm.stride(1), obs_dim - 2), obs_dim - 2
     else:
         src, ks = dense(env_obs.data_ptr(), stride, obs_dim), obs_dim
@@ -584,15 +622,16 @@ def dqn_q(dqn, env_obs, obs_dim, state, h_prev, nbr, agent_node, scratch, hidden
 
 
 @torch.no_grad()
-def dqn_q_dense(dqn, env_obs, graph, scratch):
+def dqn_q_dense(dqn, env_obs, graph, scratch, global_h=None):
     """Q [B*A, actions] of the DQN on [env obs | graph obs] given as two dense sources (the training
     target pass on the online graph observations): env_obs [B, A, od] with 16-byte rows, graph
-    [B, A, G] contiguous."""
+    [B, A, G] contiguous. global_h = H: the graph rows are [h | nbr x 3 | global] (the sequence-batched
+    update's readout buffer) instead of the reference order."""
     B, A, od = env_obs.shape
     M = B * A
     g2 = graph.reshape(M, graph.shape[-1])
     lin0 = dqn.encoder.linear_layers[0]
-    wp, ldw, b, x3 = pack_dqn_first(lin0, od)
+    wp, ldw, b, x3 = pack_dqn_first(lin0, od, global_h=global_h, order="global_env")
     h1 = scratch(0, M, lin0.out_features)
     gemm(dense(g2.data_ptr(), g2.stride(0), g2.shape[1]), dense(env_obs.data_ptr(), env_obs.stride(1), od),
          wp.data_ptr(), ldw, b.data_ptr(), M, lin0.out_features, _epi(lin0.act),

@@ -67,17 +67,27 @@ class EpsilonGreedy:
         self._decay_step()
         return actions
 
+    def _fused_q(self, wenv):
+        """Q rows of the DQN on a fused NetMonWrapper's state tables (fused.dqn_q). With the global readout the
+        dense source is the obs buffer's [env obs | global mean] columns (NetMonWrapper.global_src)."""
+        from . import fused as FU
+
+        e = wenv.env
+        if getattr(wenv, "global_cols", False):
+            return FU.dqn_q(self._model, wenv.global_src(), e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr,
+                            e.agent_node, self._buf, hidden=wenv.netmon.hidden_features, global_cols=True)
+        return FU.dqn_q(self._model, e.obs_buf, e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr,
+                        e.agent_node, self._buf, hidden=wenv.netmon.hidden_features, obs_gemm=e.obs_gemm)
+
     def act(self, wenv):
         """Fast path for a fused NetMonWrapper: the DQN's first GEMM gathers the NetMon
         readout from the node state tables instead of reading a materialised joint obs."""
-        from . import fused as FU
         from .model import DQN
 
         if not getattr(wenv, "fused", False) or not isinstance(self._model, DQN):
             return self(wenv.obs)
         e = wenv.env
-        q = FU.dqn_q(self._model, e.obs_buf, e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr,
-                     e.agent_node, self._buf, hidden=wenv.netmon.hidden_features, obs_gemm=e.obs_gemm)
+        q = self._fused_q(wenv)
         actions = self.select(q.view(e.n_env, e.n_data, -1))
         self._decay_step()
         return actions
@@ -86,7 +96,6 @@ class EpsilonGreedy:
         """act(wenv) then wenv.step_(actions). On the fused NetMon path the ε-greedy draws run
         as the env step kernel's prologue (gm_env_policy_step: one launch instead of two, the
         same draws and actions)."""
-        from . import fused as FU
         from .model import DQN
 
         if not (getattr(wenv, "fused", False) and isinstance(self._model, DQN) and FUSED_POLICY_STEP):
@@ -97,8 +106,7 @@ class EpsilonGreedy:
                 wenv.step_(actions, detail)
             return actions
         e = wenv.env
-        q = FU.dqn_q(self._model, e.obs_buf, e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr,
-                     e.agent_node, self._buf, hidden=wenv.netmon.hidden_features, obs_gemm=e.obs_gemm)
+        q = self._fused_q(wenv)
         wenv.policy_step_(q.view(e.n_env, e.n_data, -1).contiguous(), self._epsilon, self.actions, detail)
         self._decay_step()
         return self.actions

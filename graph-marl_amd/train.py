@@ -194,14 +194,18 @@ def _fused_next_q(netmon, model_tar, next_obs, next_node_obs, nbr, next_agent_no
     from . import fused as FU
 
     B, A, od = next_obs.shape
-    odp = (od + 3) // 4 * 4  # 16-byte rows for the GEMM's dense source
+    H = netmon.hidden_features
+    glob = netmon.output_global_hidden  # dense source [env obs | mean of h over the graph] (gm_netmon_global_rows)
+    odp = (od + (H if glob else 0) + 3) // 4 * 4  # 16-byte rows for the GEMM's dense source
     env_obs = next_obs.contiguous() if odp == od else F.pad(next_obs, (0, odp - od))
     keep = netmon.save_state()
     st, h_prev = FU.netmon_step(netmon, next_node_obs, nbr.contiguous(), state.detach().contiguous())
     netmon.restore_state(keep)
     dev = env_obs.device
+    if glob:
+        FU.global_rows(st.data_ptr(), st.shape[-1], B, st.shape[1], H, A, env_obs.data_ptr() + 4 * od, odp)
     q = FU.dqn_q(model_tar, env_obs, od, st, h_prev, nbr.contiguous(), next_agent_node.contiguous(),
-                 lambda i, m, n: torch.empty(m, n, device=dev), hidden=netmon.hidden_features)
+                 lambda i, m, n: torch.empty(m, n, device=dev), hidden=H, global_cols=glob)
     return q.view(B, A, -1)
 
 

@@ -32,8 +32,17 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(no carry-over, global readout, aux loss, DGN with NetMon, GM_GEMM=f32; DQNR / CommNet without NetMon:
+(no carry-over, aux loss, DGN with NetMon, GM_GEMM=f32; DQNR / CommNet without NetMon:
 agent_seq.py; DGN without NetMon: dgn_seq.py).
+
+Global readout (NetMon output_global_hidden, --netmon-global; graph observation [h | global | nbr x 3] with
+global = the mean of h over the graph's nodes, src/model.py:458-469): the readout buffer is [L*B*A, 5H] =
+[h | nbr x 3 | global]; gm_netmon_readout_ld writes the first 4H columns (ld 5H), gm_netmon_global_rows the last H
+from S[K] of all L*B graphs in one launch, and the first DQN layer's weight columns are packed in that order
+(_dqn_first_x3; its gradient is mapped back to the reference order). Backward: the layer's input gradient is 5H
+wide; gm_netmon_global_bwd adds the mean's transpose onto dh_final once over all steps, right after
+gm_netmon_readout_bwd, so the cells' backward is the same. The target pass reads the same 5H rows for steps
+0..L-2 and takes the rollout's global path (train._fused_next_q) for its own NetMon steps.
 """
 import ctypes as C
 from collections import namedtuple
@@ -64,7 +73,8 @@ def cell_ok(netmon):
 
 def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
     """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM, GRU or LayerNorm-LSTM
-    cells with carry-over, sum / mean aggregation, neighbour readout, leaky MLPs, split-f16 GEMMs."""
+    cells with carry-over, sum / mean aggregation, neighbour readout (with or without the global mean), leaky MLPs,
+    split-f16 GEMMs."""
     if netmon is None or aux_model is not None or att_coeff != 0 or L.GEMM_MODE != "x3":
         return False
     if type(model) is not MD.DQN or type(model_tar) is not MD.DQN:
@@ -74,7 +84,7 @@ def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
     dq = list(model.encoder.linear_layers)
     fc = model.q_net.fc
     return (cell_ok(netmon) and netmon.rnn_carryover and netmon.output_neighbor_hidden
-            and not netmon.output_global_hidden and netmon.iterations >= 1 and H % 32 == 0 and H <= 1024
+            and netmon.iterations >= 1 and H % 32 == 0 and H <= 1024
             and all(l.act == 1 for l in enc) and all(l.act == 1 for l in dq) and fc.act == 0
             and fc.out_features <= 4 and all(l.bias is not None for l in enc + dq + [fc])
             and dq[-1].out_features <= 1024)
@@ -127,13 +137,28 @@ def _lin_x3t(lin, cols=None):
     return _cache(lin).get(("t", None if cols is None else (cols.start, cols.stop)), FU._key(lin.weight), build)
 
 
-def _dqn_first_x3(lin, od):
-    """First DQN layer with columns reordered to [graph | env obs] (the GEMM's two sources)."""
+def _dqn_first_x3(lin, od, global_h=None):
+    """First DQN layer with columns reordered to [graph | env obs] (the GEMM's two sources); global_h = H (global
+    readout): [h | nbr x 3 | global | env obs] (FU.global_first_cols)."""
     def build():
         with torch.no_grad():
+            if global_h is not None:
+                return _x3(FU.global_first_cols(lin.weight, od, global_h, "global_env"))
             w = torch.cat([lin.weight[:, od:], lin.weight[:, :od]], 1)
             return _x3(w)
-    return _cache(lin).get(("first", od), FU._key(lin.weight), build)
+    return _cache(lin).get(("first", od, global_h), FU._key(lin.weight), build)
+
+
+def _dqn_first_x3t(lin, od, H, glob):
+    """X3 of W[:, graph columns]^T for the first DQN layer's graph-input gradient, the columns in the readout
+    buffer's order ([h | nbr x 3], with the global readout [h | nbr x 3 | global])."""
+    if not glob:
+        return _lin_x3t(lin, slice(od, od + 4 * H))
+
+    def build():
+        w = FU.global_first_cols(lin.weight.detach(), od, H, "global_env")[:, :5 * H]
+        return _x3(w.t().contiguous())
+    return _cache(lin).get(("t_global", od, H), FU._key(lin.weight), build)
 
 
 def _lstm_x3t(cell):
@@ -404,10 +429,15 @@ def _forward(p):
     p.S_in, p.S, p.act, p.agg, p.s_obs, p.s_upd = S_in, S, act, agg, s_obs, s_upd
 
     # ---- readout + DQN over all steps ----
-    R = torch.empty(LMa, 4 * H, device=dev)
+    glob = netmon.output_global_hidden
+    GW = (5 if glob else 4) * H  # readout row: [h | nbr x 3], global readout: [h | nbr x 3 | global]
+    p.glob, p.GW = glob, GW
+    R = torch.empty(LMa, GW, device=dev)
     hp = S[K - 1] if K >= 1 else torch.zeros_like(S[K])
     L.check(lib.gm_netmon_readout_ld(S[K].data_ptr(), S2, hp.data_ptr(), S2, nbr.data_ptr(), an.data_ptr(), Ls * B, N,
-                                     A, deg, H, R.data_ptr(), 4 * H, L.stream_ptr()))
+                                     A, deg, H, R.data_ptr(), GW, L.stream_ptr()))
+    if glob:
+        FU.global_rows(S[K].data_ptr(), S2, Ls * B, N, H, A, R.data_ptr() + 16 * H, GW)
     p.R = R
     env = sb.obs.reshape(LMa, odp)
     p.env = env
@@ -424,8 +454,8 @@ def _forward(p):
         yb = None if last else _sign_bits(LMa, n, dev)
         p.d_bits.append(yb)
         if i == 0:
-            _gemm_amax(R, 4 * H, 4 * H, _dqn_first_x3(lin, od), lin.bias, LMa, n, FU.GM_EPI_BIAS_LEAKY, y, n, sx,
-                       a1=(env, odp, od), sbits=yb)
+            _gemm_amax(R, GW, GW, _dqn_first_x3(lin, od, H if glob else None), lin.bias, LMa, n,
+                       FU.GM_EPI_BIAS_LEAKY, y, n, sx, a1=(env, odp, od), sbits=yb)
             if last:
                 torch.addmm(fc.bias.detach(), y, fc.weight.detach().t(), out=q)
         elif last and n <= 256:  # last hidden layer + Q head in one kernel (hidden output written too)
@@ -681,17 +711,24 @@ def _backward(p, dq):
         g, sc = gn, _finish(gmax)
     lin0 = dl[0]
     s_in0 = p.d_in_scale[0]
-    w_r, w_env = MD._wgrad_pair(g, p.R, 4 * H, p.env, od, sc, s_in0, s_in0)  # one launch: g read once per k chunk
-    grads[lin0.weight] = torch.cat([w_env, w_r], 1)
-    dR = torch.empty(LMa, 4 * H, device=dev)
-    _dgrad(g, lin0.out_features, lin0.out_features, sc, _lin_x3t(lin0, slice(od, od + 4 * H)), LMa, 4 * H, 4 * H,
-           None, 0, dR, 4 * H)
+    glob, GW = p.glob, p.GW
+    w_r, w_env = MD._wgrad_pair(g, p.R, GW, p.env, od, sc, s_in0, s_in0)  # one launch: g read once per k chunk
+    # the reference's column order: [env | h | nbr x 3], with the global readout [env | h | global | nbr x 3]
+    grads[lin0.weight] = (torch.cat([w_env, w_r[:, :H], w_r[:, 4 * H:], w_r[:, H:4 * H]], 1) if glob
+                          else torch.cat([w_env, w_r], 1))
+    dR = torch.empty(LMa, GW, device=dev)
+    _dgrad(g, lin0.out_features, lin0.out_features, sc, _dqn_first_x3t(lin0, od, H, glob), LMa, GW, GW,
+           None, 0, dR, GW)
 
     # ---- readout over all steps ----
     dhf = torch.empty(LM, H, device=dev)
     dhp = torch.empty(LM, H, device=dev)
-    L.check(lib.gm_netmon_readout_bwd(dR.data_ptr(), 4 * H, p.nbr.data_ptr(), p.an.data_ptr(), Ls * B, N, A,
+    L.check(lib.gm_netmon_readout_bwd(dR.data_ptr(), GW, p.nbr.data_ptr(), p.an.data_ptr(), Ls * B, N, A,
                                       p.nbr.shape[-1], H, dhf.data_ptr(), dhp.data_ptr(), L.stream_ptr()))
+    if glob:  # the mean's transpose, added onto dh_final for every node of the graph
+        with L.timed(f"gm_netmon_global_bwd:{LM}x{H}"):
+            L.check(lib.gm_netmon_global_bwd(dR.data_ptr() + 16 * H, GW, Ls * B, N, H, A, dhf.data_ptr(), H,
+                                             L.stream_ptr()))
 
     # ---- recurrent cells, per step, in reverse ----
     if netmon.rnn_type == "gru":
@@ -829,8 +866,9 @@ def _target_max(p, model_tar, gamma_unused=None):
     out = torch.empty(Ls, B, A, device=dev)
     if Ls > 1:
         env = sb.obs[1:].reshape((Ls - 1) * B, A, odp)[..., :od]
-        graph = p.R[Ma:].view((Ls - 1) * B, A, 4 * H)
-        q = FU.dqn_q_dense(model_tar, env, graph, lambda i, m, n: torch.empty(m, n, device=dev))
+        graph = p.R[Ma:].view((Ls - 1) * B, A, p.GW)
+        q = FU.dqn_q_dense(model_tar, env, graph, lambda i, m, n: torch.empty(m, n, device=dev),
+                           global_h=H if p.glob else None)
         out[:-1] = q.view(Ls - 1, B, A, -1).max(dim=-1)[0]
         done_rows = sb.episode_done[:-1].nonzero().cpu()  # one host read per update
         for t in torch.unique(done_rows[:, 0]).tolist():

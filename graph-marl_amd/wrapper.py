@@ -9,6 +9,15 @@ observation is NOT materialised — the DQN gathers it inside its first GEMM
 (policy.EpsilonGreedy.act). Reading `.obs` (the reference API) materialises the joint
 observation [env obs | readout] on demand. Unfused mode runs NetMon.forward_graph and writes
 the readout into the joint observation buffer after every step.
+
+Global readout (NetMon output_global_hidden, --netmon-global), fused mode: the joint observation is
+[env obs | h | global | nbr x 3] with global = the mean of h over the graph's nodes. After every NetMon step
+gm_netmon_global_rows writes that mean into the H columns that directly follow the env observation in the obs
+buffer (the columns where a materialised observation holds h), so the DQN's first GEMM reads its dense source
+[env obs | global] from the buffer's rows and gathers [h | nbr x 3] from the state tables. The GEMM-ready env copy
+has no spare columns, so it is not enabled. Reading `.obs` overwrites the scratch columns with the reference
+layout; the next fused Q pass (global_src) writes the mean back first. Both directions are tracked (`_dirty`,
+`_gstale`), so `.obs` reads and policy.act calls may alternate freely between env steps.
 """
 import torch
 
@@ -38,14 +47,18 @@ class NetMonWrapper:
         if fused is None:
             fused = FU.fused_ok(netmon)
         self.fused = fused
-        if fused and hasattr(env, "enable_gemm_obs"):
+        # fused global readout: the obs buffer's first H graph columns are the DQN's scratch for the mean
+        self.global_cols = bool(fused and netmon.output_global_hidden)
+        if fused and hasattr(env, "enable_gemm_obs") and not self.global_cols:
             env.enable_gemm_obs()  # the fused DQN reads the GEMM-ready env obs copy
         self._dirty = False
+        self._gstale = False  # global_cols: the scratch columns do not hold the current state's mean
         # fused mode: the state and h_prev alternate between two fixed buffer pairs, so a
         # captured 2-step HIP graph (rollout.StreamedRollout.capture) reads and writes the
         # same addresses on every replay
         self._bufs = None
         self._cur = 0
+        self._rd = None  # global_cols: the 4H readout rows of _materialize
 
     def __getattr__(self, name):
         return getattr(self.env, name)
@@ -65,11 +78,44 @@ class NetMonWrapper:
     def _materialize(self):
         e, H = self.env, self.netmon.hidden_features
         B, N = e.n_env, e.n_nodes
+        if self.global_cols:  # [h | global | nbr x 3]: the 4H readout rows, then h and the mean into their columns
+            A, deg = e.n_data, e.nbr.shape[-1]
+            st = self.current_netmon_state
+            ob = e.obs_buf.data_ptr() + 4 * e.obs_dim
+            if self._rd is None:
+                self._rd = torch.empty(B * A, (deg + 1) * H, device=e.device)
+            with torch.no_grad():
+                L.check(L.lib().gm_netmon_readout_ld(st.data_ptr(), st.shape[-1], self.h_prev.data_ptr(),
+                                                     self.h_prev.stride(0), e.nbr.data_ptr(), e.agent_node.data_ptr(),
+                                                     B, N, A, deg, H, self._rd.data_ptr(), self._rd.stride(0),
+                                                     L.stream_ptr()))
+                g = e.obs_buf.view(B * A, -1)[:, e.obs_dim:e.obs_dim + (deg + 2) * H]
+                g[:, :H] = self._rd[:, :H]
+                g[:, 2 * H:] = self._rd[:, H:]
+                FU.global_rows(st.data_ptr(), st.shape[-1], B, N, H, A, ob + 4 * H, e.obs_stride)
+            self._dirty = False
+            self._gstale = True
+            return
         hf = self.current_netmon_state.reshape(B * N, -1)[:, :H].contiguous()
         hp = self.h_prev[:, :H].contiguous()
         with torch.no_grad():
             netmon_readout(hf, hp, e.nbr, e.agent_node, out=e.obs_buf, col0=e.obs_dim)
         self._dirty = False
+
+    def global_src(self):
+        """The obs buffer for fused.dqn_q(global_cols=True): its rows hold [env obs | global mean] for the current
+        NetMon state (rewritten here when a `.obs` read has put the reference layout over it)."""
+        if self._gstale:
+            self._write_global()
+        return self.env.obs_buf
+
+    def _write_global(self):
+        e, H = self.env, self.netmon.hidden_features
+        st = self.current_netmon_state
+        FU.global_rows(st.data_ptr(), st.shape[-1], e.n_env, e.n_nodes, H, e.n_data,
+                       e.obs_buf.data_ptr() + 4 * e.obs_dim, e.obs_stride)
+        self._gstale = False
+        self._dirty = True  # the scratch sits where the materialised observation holds h
 
     def _netmon_step(self):
         e = self.env
@@ -86,6 +132,8 @@ class NetMonWrapper:
                                                     out=st, last_out=hp)
                 self._cur = nxt
                 self.current_netmon_state = state
+                if self.global_cols:
+                    self._write_global()
                 self._dirty = True
             else:
                 self.netmon.state = self.current_netmon_state

@@ -442,6 +442,19 @@ int gm_qhead_bwd(const float* dq, int64_t ldq, int32_t nq, const float* wq, int6
 int gm_netmon_readout_ld(const float* h_final, int64_t ldf, const float* h_prev, int64_t ldp, const int32_t* nbr,
                          const int32_t* agent_node, int32_t n_graphs, int32_t n_nodes, int32_t n_rows, int32_t deg,
                          int32_t hidden, float* out, int64_t out_stride, void* stream);
+/* Global-mean readout (NetMon with output_global_hidden, src/model.py:458-469, 624-627): for graph b and column
+ * j < hidden, m = (1 / n_nodes) * sum_n state[(b * n_nodes + n) * ld_state + j], summed in ascending node order in
+ * fp32 (independent of the launch shape), written to out[(b * rows_per_graph + r) * ld_out + j] for every
+ * r < rows_per_graph (the agent rows of the graph, or n_nodes for the unmapped readout). out may start at any
+ * 4-byte aligned column of a wider row; the other columns are not touched. hidden % 32 == 0, hidden <= 1024,
+ * n_nodes <= 128; outside these limits GM_ERR_INVALID_ARG and nothing is launched. */
+int gm_netmon_global_rows(const float* state, int64_t ld_state, int32_t n_graphs, int32_t n_nodes, int32_t hidden,
+                          int32_t rows_per_graph, float* out, int64_t ld_out, void* stream);
+/* Its backward, accumulated onto dh (launched after gm_netmon_readout_bwd wrote dh_final, on the same stream):
+ * dh[(b * n_nodes + n) * ld_dh + j] += (1 / n_nodes) * sum_r d_rows[(b * rows_per_graph + r) * ld_d + j] for every
+ * node n, the r sum in ascending order. The same limits. */
+int gm_netmon_global_bwd(const float* d_rows, int64_t ld_d, int32_t n_graphs, int32_t n_nodes, int32_t hidden,
+                         int32_t rows_per_graph, float* dh, int64_t ld_dh, void* stream);
 /* Fused f32 MFMA linear layer: y[M,N] = act(x[M,K] @ w[N,K]^T + b[N]); row strides ldx, ldw
  * (multiples of 4 floats, 16-byte aligned bases), ldy; K may be ragged; b nullable;
  * act 0 = none, 1 = leaky_relu(0.01). */
