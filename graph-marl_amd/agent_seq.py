@@ -24,8 +24,8 @@ one autograd node over the whole sequence (`_AgentSeqFn`), organised like train_
     the obs cell's dx rows of all steps land in one buffer, masked by the encoder's last leaky derivative, for the
     batched encoder backward.
 
-Every other configuration (NetMon, aux loss, GM_GEMM=f32) keeps train.dqn_loss; DGN without NetMon, attention
-regularisation included, has its own batched update (dgn_seq.py).
+Every other configuration (DQNR / CommNet with NetMon, aux loss, GM_GEMM=f32) keeps train.dqn_loss; DGN, attention
+regularisation included, has its own batched updates (dgn_seq.py without NetMon, dgn_netmon_seq.py with it).
 """
 import ctypes as C
 from collections import namedtuple

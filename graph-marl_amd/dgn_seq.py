@@ -24,7 +24,8 @@ organised like agent_seq.py:
     gradient; then the batched encoder backward.
 
 Every GEMM runs in the split-f16 form with fp32 accumulation, as in train.dqn_loss, which remains the path for every
-other configuration (DGN with NetMon, other activations, aux loss, GM_GEMM=f32, more than 64 agents).
+other configuration (other activations, aux loss, GM_GEMM=f32, more than 64 agents). DGN with NetMon:
+dgn_netmon_seq.py, which calls _forward / _backward here with the encoder's first layer in its own hands (`first`).
 """
 from collections import namedtuple
 
@@ -94,7 +95,9 @@ def _qkv_ptrs(buf, layer):
     return p + 4 * nh * (dv + dk), p + 4 * nh * dv, p
 
 
-def _forward(p):
+def _forward(p, first=None):
+    """first (dgn_netmon_seq.py): the encoder's first layer in the caller's hands, first(lin, y, ldy, sign bits) ->
+    the zeroed max |input| slot its GEMM published into; the env observation rows are then not read here."""
     model, sb = p.model, p.seq
     dev = sb.obs.device
     Ls, B, A, odp = sb.obs.shape
@@ -105,21 +108,24 @@ def _forward(p):
     LM = Ls * B * A
     p.dims = (Ls, B, A, od, hid, nl, Hq, LM)
     lib = L.lib()
-    X = AS._rows16(sb.obs.reshape(LM, odp), od)
+    X = AS._rows16(sb.obs.reshape(LM, odp), od) if first is None else None
     qin = torch.empty(LM, Hq, device=dev)  # [h_enc | h_1 | ...]: the head's input, every segment a leaky output
     p.qin = qin
 
     # ---- encoder over all rows, the last layer into segment 0 ----
     enc = list(model.encoder.linear_layers)
     p.enc_in, p.enc_bits, p.bits = [], [], []
-    x, ldx, kx = X, X.stride(0), od
+    x, ldx, kx = (X, X.stride(0), od) if first is None else (None, 0, 0)
     for i, lin in enumerate(enc):
         n = lin.out_features
         last = i == len(enc) - 1
         y, ldy = (qin, Hq) if last else (torch.empty(LM, n, device=dev), n)
         yb = TS._sign_bits(LM, n, dev)
-        sx = TS._zeros1(dev)
-        TS._gemm_amax(x, ldx, kx, TS._lin_x3(lin), lin.bias, LM, n, FU.GM_EPI_BIAS_LEAKY, y, ldy, sx, sbits=yb)
+        if i == 0 and first is not None:
+            sx = first(lin, y, ldy, yb)
+        else:
+            sx = TS._zeros1(dev)
+            TS._gemm_amax(x, ldx, kx, TS._lin_x3(lin), lin.bias, LM, n, FU.GM_EPI_BIAS_LEAKY, y, ldy, sx, sbits=yb)
         p.enc_in.append((x, ldx, kx, TS._finish(sx)))
         if last:
             p.bits.append(yb)  # bits[s]: the sign bits of segment s
@@ -174,7 +180,9 @@ def _forward(p):
     return q, kl
 
 
-def _backward(p, dq, r):
+def _backward(p, dq, r, first=None):
+    """first (dgn_netmon_seq.py): first(lin, g, its scale, the layer input's scale, grads) takes the encoder's first
+    layer's weight gradient (and whatever lies below it) in place of the one-source weight gradient here."""
     model = p.model
     Ls, B, A, od, hid, nl, Hq, LM = p.dims
     dev = dq.device
@@ -253,7 +261,10 @@ def _backward(p, dq, r):
     for i in range(len(enc) - 1, -1, -1):
         lin = enc[i]
         xin, ldx, kin, sxi = p.enc_in[i]
-        grads[lin.weight] = TS._wgrad(g, sc, xin, kin, sxi)
+        if i == 0 and first is not None:
+            first(lin, g, sc, sxi, grads)
+        else:
+            grads[lin.weight] = TS._wgrad(g, sc, xin, kin, sxi)
         if i > 0:
             gn = torch.empty(LM, kin, device=dev)
             part = torch.empty((LM + 127) // 128, kin, device=dev)

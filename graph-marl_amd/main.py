@@ -59,6 +59,7 @@ T = importlib.import_module("graph-marl_amd.train")
 TS = importlib.import_module("graph-marl_amd.train_seq")
 AS = importlib.import_module("graph-marl_amd.agent_seq")
 DS = importlib.import_module("graph-marl_amd.dgn_seq")
+DNS = importlib.import_module("graph-marl_amd.dgn_netmon_seq")
 RB = importlib.import_module("graph-marl_amd.replaybuffer")
 S = importlib.import_module("graph-marl_amd.simple")
 HEU = importlib.import_module("graph-marl_amd.heuristics")
@@ -496,6 +497,14 @@ def _main(args, rank, world):
                                                                                args.sequence_length),
                                                         args.gamma, args.tau, args.target_update_steps, iteration,
                                                         att_coeff=att, parts=parts)
+                qs, qts = list(q_all), list(qt_all)
+            elif DNS.dgn_netmon_seq_ok(netmon, model, model_tar, att, aux_model, n_agents):
+                # DGN on NetMon graph observations, at every sequence length: the NetMon unroll of
+                # train_seq.py and the DGN rows of dgn_seq.py as one autograd node (dgn_netmon_seq.py)
+                loss, q_all, qt_all = DNS.dgn_netmon_update_seq(
+                    netmon, model, model_tar, optimizer, params,
+                    buff.get_dgn_netmon_sequences(args.mini_batch_size, args.sequence_length), args.gamma, args.tau,
+                    args.target_update_steps, iteration, att_coeff=att, parts=parts)
                 qs, qts = list(q_all), list(qt_all)
             else:
                 batches = list(buff.get_batch(args.mini_batch_size, sequence_length=args.sequence_length,

@@ -32,8 +32,9 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(no carry-over, aux loss, DGN with NetMon, GM_GEMM=f32; DQNR / CommNet without NetMon:
-agent_seq.py; DGN without NetMon: dgn_seq.py).
+(no carry-over, aux loss, DQNR / CommNet with NetMon, GM_GEMM=f32; DQNR / CommNet without NetMon:
+agent_seq.py; DGN without NetMon: dgn_seq.py; DGN with NetMon: dgn_netmon_seq.py, which runs the NetMon half of this
+module, _forward_netmon / _backward_netmon, around the DGN half of dgn_seq.py).
 
 Global readout (NetMon output_global_hidden, --netmon-global; graph observation [h | global | nbr x 3] with
 global = the mean of h over the graph's nodes, src/model.py:458-469): the readout buffer is [L*B*A, 5H] =
@@ -71,6 +72,16 @@ def cell_ok(netmon):
             or (netmon.rnn_type == "lnlstm" and H <= 512))
 
 
+def netmon_seq_ok(netmon):
+    """The NetMon half's conditions (shared with dgn_netmon_seq.py): a cell cell_ok takes, carry-over, the neighbour
+    readout, K >= 1, H % 32 == 0, a leaky encoder with biases."""
+    H = netmon.hidden_features
+    enc = list(netmon.encode.linear_layers)
+    return (cell_ok(netmon) and netmon.rnn_carryover and netmon.output_neighbor_hidden
+            and netmon.iterations >= 1 and H % 32 == 0 and H <= 1024
+            and all(l.act == 1 and l.bias is not None for l in enc))
+
+
 def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
     """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM, GRU or LayerNorm-LSTM
     cells with carry-over, sum / mean aggregation, neighbour readout (with or without the global mean), leaky MLPs,
@@ -79,14 +90,10 @@ def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
         return False
     if type(model) is not MD.DQN or type(model_tar) is not MD.DQN:
         return False
-    H = netmon.hidden_features
-    enc = list(netmon.encode.linear_layers)
     dq = list(model.encoder.linear_layers)
     fc = model.q_net.fc
-    return (cell_ok(netmon) and netmon.rnn_carryover and netmon.output_neighbor_hidden
-            and netmon.iterations >= 1 and H % 32 == 0 and H <= 1024
-            and all(l.act == 1 for l in enc) and all(l.act == 1 for l in dq) and fc.act == 0
-            and fc.out_features <= 4 and all(l.bias is not None for l in enc + dq + [fc])
+    return (netmon_seq_ok(netmon) and all(l.act == 1 for l in dq) and fc.act == 0
+            and fc.out_features <= 4 and all(l.bias is not None for l in dq + [fc])
             and dq[-1].out_features <= 1024)
 
 
@@ -309,8 +316,11 @@ class _Plan:
     pass
 
 
-def _forward(p):
-    netmon, dqn = p.netmon, p.dqn
+def _forward_netmon(p):
+    """The NetMon half of the forward (p.netmon on p.seq), up to and including the readout buffer: returns p.R
+    [L*B*A, GW] = [h | nbr x 3] (global readout: [h | nbr x 3 | global]); sets p.dims, p.env (the env obs rows) and
+    the tensors _backward_netmon reads."""
+    netmon = p.netmon
     sb = p.seq
     dev = sb.obs.device
     Ls, B, A, odp = sb.obs.shape
@@ -428,7 +438,7 @@ def _forward(p):
     _finish(s_upd)
     p.S_in, p.S, p.act, p.agg, p.s_obs, p.s_upd = S_in, S, act, agg, s_obs, s_upd
 
-    # ---- readout + DQN over all steps ----
+    # ---- readout over all steps ----
     glob = netmon.output_global_hidden
     GW = (5 if glob else 4) * H  # readout row: [h | nbr x 3], global readout: [h | nbr x 3 | global]
     p.glob, p.GW = glob, GW
@@ -439,8 +449,19 @@ def _forward(p):
     if glob:
         FU.global_rows(S[K].data_ptr(), S2, Ls * B, N, H, A, R.data_ptr() + 16 * H, GW)
     p.R = R
-    env = sb.obs.reshape(LMa, odp)
-    p.env = env
+    p.env = sb.obs.reshape(LMa, odp)
+    return R
+
+
+def _forward(p):
+    R = _forward_netmon(p)
+    dqn = p.dqn
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
+    LMa = Ls * Ma
+    dev = R.device
+    glob, GW, env = p.glob, p.GW, p.env
+
+    # ---- DQN over all steps ----
     dl = list(dqn.encoder.linear_layers)
     fc = dqn.q_net.fc
     nq = fc.out_features
@@ -666,11 +687,10 @@ def _lnlstm_cells_bwd(p, dhf, dhp, grads):
 
 
 def _backward(p, dq):
-    netmon, dqn = p.netmon, p.dqn
+    dqn = p.dqn
     Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
-    S2 = 2 * H  # (lstm branch)
     dev = dq.device
-    LM, LMa = Ls * M, Ls * Ma
+    LMa = Ls * Ma
     lib = L.lib()
     grads = {}
     dq = dq.contiguous()
@@ -719,6 +739,20 @@ def _backward(p, dq):
     dR = torch.empty(LMa, GW, device=dev)
     _dgrad(g, lin0.out_features, lin0.out_features, sc, _dqn_first_x3t(lin0, od, H, glob), LMa, GW, GW,
            None, 0, dR, GW)
+    return _backward_netmon(p, dR, grads)
+
+
+def _backward_netmon(p, dR, grads):
+    """The NetMon half of the backward from dR [L*B*A, GW], the gradient of the readout buffer p.R: the readout's
+    transpose, the cells per step in reverse, the batched encoder backward. Adds NetMon's parameter gradients to
+    grads and returns it."""
+    netmon = p.netmon
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
+    S2 = 2 * H  # (lstm branch)
+    dev = dR.device
+    LM = Ls * M
+    lib = L.lib()
+    glob, GW = p.glob, p.GW
 
     # ---- readout over all steps ----
     dhf = torch.empty(LM, H, device=dev)
