@@ -24,8 +24,10 @@ one autograd node over the whole sequence (`_AgentSeqFn`), organised like train_
     the obs cell's dx rows of all steps land in one buffer, masked by the encoder's last leaky derivative, for the
     batched encoder backward.
 
-Every other configuration (DQNR / CommNet with NetMon, aux loss, GM_GEMM=f32) keeps train.dqn_loss; DGN, attention
-regularisation included, has its own batched updates (dgn_seq.py without NetMon, dgn_netmon_seq.py with it).
+DQNR / CommNet on NetMon graph observations: agent_netmon_seq.py, which calls _forward / _backward / _target_max here
+with the encoder's first layer in its own hands (`first`, `encode`). Every other configuration (aux loss, GM_GEMM=f32)
+keeps train.dqn_loss; DGN, attention regularisation included, has its own batched updates (dgn_seq.py without NetMon,
+dgn_netmon_seq.py with it).
 """
 import ctypes as C
 from collections import namedtuple
@@ -120,7 +122,9 @@ def _comm(h_rows, adj, n_env, A, H, out):
                                   out.stride(0), L.stream_ptr()))
 
 
-def _forward(p):
+def _forward(p, first=None):
+    """first (agent_netmon_seq.py): the encoder's first layer in the caller's hands, first(lin, y, ldy, sign bits) ->
+    the zeroed max |input| slot its GEMM published into; the env observation rows are then not read here."""
     model, sb = p.model, p.seq
     dev = sb.obs.device
     Ls, B, A, odp = sb.obs.shape
@@ -130,18 +134,23 @@ def _forward(p):
     M = B * A
     LM = Ls * M
     p.dims = (Ls, B, A, od, H, R, M)
-    X = _rows16(sb.obs.reshape(LM, odp), od)
+    X = _rows16(sb.obs.reshape(LM, odp), od) if first is None else None
 
     # ---- encoder over all steps ----
     enc = list(model.encoder.linear_layers)
     p.enc_in, p.enc_out, p.enc_bits = [], [], []
-    x, ldx, kx = X, X.stride(0), od
-    for lin in enc:
+    x, ldx, kx = (X, X.stride(0), od) if first is None else (None, 0, 0)
+    for i, lin in enumerate(enc):
         n = lin.out_features
         y = torch.empty(LM, n, device=dev)
         yb = TS._sign_bits(LM, n, dev)  # the leaky mask of this output for the backward
-        sx = TS._zeros1(dev)
-        TS._gemm_amax(x, ldx, kx, TS._lin_x3(lin), lin.bias, LM, n, FU.GM_EPI_BIAS_LEAKY, y, n, sx, sbits=yb)
+        if i == 0 and first is not None:
+            sx = first(lin, y, n, yb)
+        else:
+            sx = TS._zeros1(dev)
+            TS._gemm_amax(x, ldx, kx, TS._lin_x3(lin), lin.bias, LM, n, FU.GM_EPI_BIAS_LEAKY, y, n, sx, sbits=yb)
+        # with a `first` hook layer 0's entry is (None, 0, 0, scale): _backward hands that layer to its own hook and
+        # never reads the input rows
         p.enc_in.append((x, ldx, kx, TS._finish(sx)))
         p.enc_out.append(y)
         p.enc_bits.append(yb)
@@ -176,7 +185,9 @@ def _forward(p):
     return q
 
 
-def _backward(p, dq):
+def _backward(p, dq, first=None):
+    """first (agent_netmon_seq.py): first(lin, g, its scale, the layer input's scale, grads) takes the encoder's first
+    layer's weight gradient (and whatever lies below it) in place of the one-source weight gradient here."""
     model, sb = p.model, p.seq
     Ls, B, A, od, H, R, M = p.dims
     dev = dq.device
@@ -282,7 +293,10 @@ def _backward(p, dq):
     for i in range(len(enc) - 1, -1, -1):
         lin = enc[i]
         xin, ldx, kin, sxi = p.enc_in[i]
-        grads[lin.weight] = TS._wgrad(g, sc, xin, kin, sxi)
+        if i == 0 and first is not None:
+            first(lin, g, sc, sxi, grads)
+        else:
+            grads[lin.weight] = TS._wgrad(g, sc, xin, kin, sxi)
         if i > 0:
             gn = torch.empty(LM, kin, device=dev)
             part = torch.empty((LM + 127) // 128, kin, device=dev)
@@ -311,17 +325,21 @@ class _AgentSeqFn(torch.autograd.Function):
 
 
 @torch.no_grad()
-def _target_max(p, model_tar):
+def _target_max(p, model_tar, encode=None):
     """max_a Q_target(next obs) [L, B, A]: the target model starts step t from the online model's state after
     step t, before the done / episode-end mask (src/main.py:899-902), and carries nothing from step to step, so
     all L steps are one pass over L*B*A rows: encoder on the stored next observations, one LSTM cell, CommNet's
-    rounds on next_adj, head, max."""
+    rounds on next_adj, head, max. encode (agent_netmon_seq.py): encode(encoder, rows, scratch) -> the target
+    encoder's output rows, in place of the encoder pass on the stored next observations."""
     Ls, B, A, od, H, R, M = p.dims
     sb = p.seq
     dev = sb.next_obs.device
     LM = Ls * M
-    X = _rows16(sb.next_obs.reshape(LM, sb.next_obs.shape[-1]), od)
-    E = FU.mlp_rows(model_tar.encoder, X, X.stride(0), od, LM, MD._scratch_dict({}))
+    if encode is None:
+        X = _rows16(sb.next_obs.reshape(LM, sb.next_obs.shape[-1]), od)
+        E = FU.mlp_rows(model_tar.encoder, X, X.stride(0), od, LM, MD._scratch_dict({}))
+    else:
+        E = encode(model_tar.encoder, LM, MD._scratch_dict({}))
     st = p.S[R].view(LM, 2 * H)
     S = torch.empty(LM, 2 * H, device=dev)
     _cell_fwd(model_tar.lstm, E, st[:, :H], st[:, H:], S)

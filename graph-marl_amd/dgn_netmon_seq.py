@@ -88,6 +88,53 @@ def _next_graph_rows(pn):
     return Rn.view(Ls * Ma, GW)
 
 
+def target_first(pn, lin, Rn, env, dst):
+    """The target model's first encoder layer on its two dense sources [next graph rows Rn | next env obs rows env]
+    into the rows dst (no-grad; the weight packed as fused.pack_dqn_first packs it for dense graph rows)."""
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = pn.dims
+    LM, GW, n = Ls * Ma, pn.GW, lin.out_features
+    wp, ldw, b, x3 = FU.pack_dqn_first(lin, od, global_h=H if pn.glob else None, order="global_env")
+    FU.gemm(FU.dense(Rn.data_ptr(), GW, GW), FU.dense(env.data_ptr(), odp, od), wp.data_ptr(), ldw,
+            b.data_ptr(), LM, n, FU._epi(lin.act), dst.data_ptr(), dst.stride(0),
+            tag=lin.tag and f"linear:{lin.tag}:{LM}x{n}x{GW}+{od}", x3=x3)
+
+
+def first_forward(pn):
+    """The `first` hook of dgn_seq._forward / agent_seq._forward on NetMon graph observations: the online encoder's
+    first layer on its two sources [readout rows pn.R | env obs rows pn.env]."""
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = pn.dims
+    R, GW, glob = pn.R, pn.GW, pn.glob
+
+    def first(lin, y, ldy, yb):
+        sx = TS._zeros1(R.device)
+        TS._gemm_amax(R, GW, GW, TS._dqn_first_x3(lin, od, H if glob else None), lin.bias, Ls * Ma, lin.out_features,
+                      FU.GM_EPI_BIAS_LEAKY, y, ldy, sx, a1=(pn.env, odp, od), sbits=yb)
+        return sx
+
+    return first
+
+
+def first_backward(pn, hold):
+    """The `first` hook of dgn_seq._backward / agent_seq._backward: the first layer's weight gradient from its two
+    sources in one launch, mapped back to the reference column order, and hold["dR"] = its input gradient over the
+    readout columns, for train_seq._backward_netmon."""
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = pn.dims
+    GW, glob = pn.GW, pn.glob
+    LMa = Ls * Ma
+
+    def first(lin, g, sc, s_in, grads):
+        w_r, w_env = MD._wgrad_pair(g, pn.R, GW, pn.env, od, sc, s_in, s_in)  # one launch
+        # the reference's column order: [env | h | nbr x 3], with the global readout [env | h | global | nbr x 3]
+        grads[lin.weight] = (torch.cat([w_env, w_r[:, :H], w_r[:, 4 * H:], w_r[:, H:4 * H]], 1) if glob
+                             else torch.cat([w_env, w_r], 1))
+        dR = torch.empty(LMa, GW, device=g.device)
+        TS._dgrad(g, lin.out_features, lin.out_features, sc, TS._dqn_first_x3t(lin, od, H, glob), LMa, GW, GW,
+                  None, 0, dR, GW)
+        hold["dR"] = dR
+
+    return first
+
+
 @torch.no_grad()
 def _target(pn, pd, model_tar):
     """max_a Q_target [L, B, A] of the target DGN on [next graph obs | next env obs] with next_adj, all L steps'
@@ -112,10 +159,7 @@ def _target(pn, pd, model_tar):
         n = lin.out_features
         dst = qin if i == len(layers) - 1 else scratch(("mlp", id(model_tar.encoder), i), LM, n)
         if i == 0:
-            wp, ldw, b, x3 = FU.pack_dqn_first(lin, od, global_h=H if pn.glob else None, order="global_env")
-            FU.gemm(FU.dense(Rn.data_ptr(), GW, GW), FU.dense(env.data_ptr(), odp, od), wp.data_ptr(), ldw,
-                    b.data_ptr(), LM, n, FU._epi(lin.act), dst.data_ptr(), dst.stride(0),
-                    tag=lin.tag and f"linear:{lin.tag}:{LM}x{n}x{GW}+{od}", x3=x3)
+            target_first(pn, lin, Rn, env, dst)
         else:
             FU.linear_rows(lin, h, ld, LM, dst, dst.stride(0), k=kk)
         h, ld, kk = dst, dst.stride(0), n
@@ -132,37 +176,14 @@ def _target(pn, pd, model_tar):
 
 def _forward(pn, pd):
     """(q [L*B*A, nq], kl [L*B*A] or None); pd.next_max = the target pass's max_a Q [L, B, A]."""
-    R = TS._forward_netmon(pn)
-    Ls, B, A, N, F, od, odp, H, K, M, Ma = pn.dims
-    GW, glob = pn.GW, pn.glob
+    TS._forward_netmon(pn)
     pd.next_max = _target(pn, pd, pd.model_tar)
-
-    def first(lin, y, ldy, yb):
-        sx = TS._zeros1(R.device)
-        TS._gemm_amax(R, GW, GW, TS._dqn_first_x3(lin, od, H if glob else None), lin.bias, Ls * Ma, lin.out_features,
-                      FU.GM_EPI_BIAS_LEAKY, y, ldy, sx, a1=(pn.env, odp, od), sbits=yb)
-        return sx
-
-    return DS._forward(pd, first=first)
+    return DS._forward(pd, first=first_forward(pn))
 
 
 def _backward(pn, pd, dq, r):
-    Ls, B, A, N, F, od, odp, H, K, M, Ma = pn.dims
-    GW, glob = pn.GW, pn.glob
-    LMa = Ls * Ma
     hold = {}
-
-    def first(lin, g, sc, s_in, grads):
-        w_r, w_env = MD._wgrad_pair(g, pn.R, GW, pn.env, od, sc, s_in, s_in)  # one launch
-        # the reference's column order: [env | h | nbr x 3], with the global readout [env | h | global | nbr x 3]
-        grads[lin.weight] = (torch.cat([w_env, w_r[:, :H], w_r[:, 4 * H:], w_r[:, H:4 * H]], 1) if glob
-                             else torch.cat([w_env, w_r], 1))
-        dR = torch.empty(LMa, GW, device=g.device)
-        TS._dgrad(g, lin.out_features, lin.out_features, sc, TS._dqn_first_x3t(lin, od, H, glob), LMa, GW, GW,
-                  None, 0, dR, GW)
-        hold["dR"] = dR
-
-    grads = DS._backward(pd, dq, r, first=first)
+    grads = DS._backward(pd, dq, r, first=first_backward(pn, hold))
     TS._backward_netmon(pn, hold["dR"], grads)
     return grads
 

@@ -331,6 +331,48 @@ class ReplayBuffer:
                                  self.adj[slots, envs].to(i8), self._records(self.next_obs, slots, env),
                                  self.next_adj[slots, envs].to(i8), (slots, env))
 
+    def get_agent_netmon_sequences(self, batch_size, sequence_length):
+        """The transitions get_batch(batch_size, sequence_length) draws (same stream, same indices, for every
+        sequence_length >= 1 as get_dgn_netmon_sequences), as one agent_netmon_seq.AgentNetMonSeqBatch for DQNR /
+        CommNet on NetMon graph observations: get_dgn_netmon_sequences' fields (the adjacencies only where the buffer
+        stores them: CommNet) plus the agent state of each sequence's first slot."""
+        from .agent_netmon_seq import AgentNetMonSeqBatch
+
+        if not self.graph or self.agent_state is None:
+            raise ValueError("get_agent_netmon_sequences: NetMon transitions with the agent state only")
+        if self.count == 0:
+            raise ValueError("empty replay buffer")
+        Lq = max(1, int(sequence_length))
+        if Lq == 1:
+            f = self.choice(self.count * self.n_env, batch_size)
+            slots, env = (f // self.n_env).unsqueeze(0), f % self.n_env
+        else:
+            if self.count <= Lq:
+                raise ValueError("not enough transitions for the requested sequence length")
+            span = self.count - Lq
+            f = self.choice(self.n_env * span, batch_size)
+            env = f // span
+            first = (self.index % self.count + f % span) % self.count
+            slots = (first.unsqueeze(0) + torch.arange(Lq, device=f.device).unsqueeze(1)) % self.count  # [L, B]
+        envs = env.unsqueeze(0).expand(Lq, -1)
+        i8 = torch.int8
+
+        def next_fields(t, rows):
+            s, e = (slots[t], env) if rows is None else (slots[t][rows], env[rows])
+            return (self._records(self.next_obs, s, e), self._records(self.next_node_obs, s, e),
+                    self.next_agent_node[s, e].int().contiguous())
+
+        return AgentNetMonSeqBatch(self._records(self.obs, slots, env), self.obs_dim, self.action[slots, envs].long(),
+                                   self.reward[slots, envs].to(torch.float32), self.done[slots, envs],
+                                   self.episode_done[slots], self._records(self.node_obs, slots, env),
+                                   self.nbr[slots, envs].int().contiguous(),
+                                   self.agent_node[slots, envs].int().contiguous(),
+                                   self._records(self.node_state, slots[0], env), next_fields,
+                                   self.adj[slots, envs].to(i8) if self.adj is not None else None,
+                                   self._records(self.next_obs, slots, env),
+                                   self.next_adj[slots, envs].to(i8) if self.next_adj is not None else None,
+                                   self._records(self.agent_state, slots[0], env), (slots, env))
+
     @staticmethod
     def _records(src, slots, env):
         """src[slots, env] as float32 (slots [..., B'] int64 slot indices, env [B'] env indices): one

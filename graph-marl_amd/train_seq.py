@@ -32,8 +32,8 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(no carry-over, aux loss, DQNR / CommNet with NetMon, GM_GEMM=f32; DQNR / CommNet without NetMon:
-agent_seq.py; DGN without NetMon: dgn_seq.py; DGN with NetMon: dgn_netmon_seq.py, which runs the NetMon half of this
+(no carry-over, aux loss, GM_GEMM=f32; DQNR / CommNet without NetMon: agent_seq.py, with NetMon:
+agent_netmon_seq.py; DGN without NetMon: dgn_seq.py; DGN with NetMon: dgn_netmon_seq.py, which runs the NetMon half of this
 module, _forward_netmon / _backward_netmon, around the DGN half of dgn_seq.py).
 
 Global readout (NetMon output_global_hidden, --netmon-global; graph observation [h | global | nbr x 3] with
