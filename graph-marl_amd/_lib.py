@@ -41,7 +41,7 @@ EXPORTS = [
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
-                  "gm_last_kernel", "gm_gemm_kernel_name"]
+                  "gm_last_kernel", "gm_last_lnlstm_pw", "gm_gemm_kernel_name"]
 
 # Arithmetic form of the fused rollout GEMMs (graph-marl_amd/fused.py): "x3" = split-f16
 # MFMA with fp32 accumulation (default), "f32" = exact fp32 MFMA. GM_GEMM=f32 selects the
@@ -234,6 +234,8 @@ def lib():
         L.gm_gemm_form.restype = C.c_char_p
     if hasattr(L, "gm_last_kernel"):
         L.gm_last_kernel.restype = C.c_char_p
+    if hasattr(L, "gm_last_lnlstm_pw"):
+        L.gm_last_lnlstm_pw.restype = C.c_char_p
     if hasattr(L, "gm_gemm_kernel_name"):
         L.gm_gemm_kernel_name.argtypes = [i32]
         L.gm_gemm_kernel_name.restype = C.c_char_p
@@ -279,6 +281,12 @@ def last_kernel():
     (gm_agent_*) or GEMM call launched.
     For the dispatch tests; the product never reads it."""
     return lib().gm_last_kernel().decode()
+
+
+def last_lnlstm_pw():
+    """Diagnostic (gm_last_lnlstm_pw): the kernel this thread's most recent gm_lnlstm_fwd / gm_lnlstm_pointwise
+    launched. For the dispatch tests; the product never reads it."""
+    return lib().gm_last_lnlstm_pw().decode()
 
 
 def gemm_kernel_names():

@@ -475,6 +475,11 @@ static thread_local const char* g_last_kernel = "";
 void gm_set_last_kernel(const char* name) { g_last_kernel = name; }
 #define GM_RAN(NAME) gm_set_last_kernel(NAME)
 extern "C" const char* gm_last_kernel(void) { return g_last_kernel; }
+// gm_last_lnlstm_pw: the LayerNorm-LSTM forward names its kernel in a slot of its own. The recorded launch lists of
+// the sequence-batched update (tests/golden/*_trace.json) read gm_last_kernel after every library call, this
+// forward among them, and hold the name the call before it left there.
+static thread_local const char* g_last_lnlstm_pw = "";
+extern "C" const char* gm_last_lnlstm_pw(void) { return g_last_lnlstm_pw; }
 
 #define GM_VLAUNCH(KER, V, GRID, ...)                                                                  \
     do {                                                                                               \
@@ -1061,6 +1066,7 @@ extern "C" int gm_lstm_pointwise(const float* gates, const float* c, int32_t m, 
                                  float* act, void* stream) {
     if (!gates || !c || !h1 || !c1 || m <= 0 || H <= 0) return gm_fail(GM_ERR_INVALID_ARG, "gm_lstm_pointwise: bad args");
     long long total = (long long)m * H;
+    GM_RAN("k_lstm_pw");
     hipLaunchKernelGGL(k_lstm_pw, dim3(nblocks(total, 256)), dim3(256), 0, (hipStream_t)stream, gates, c, m, H, h1, c1,
                        act);
     return launched();
@@ -1077,6 +1083,7 @@ extern "C" int gm_lstm_pointwise_bwd(const float* dh1, const float* dc1, const f
     long long total = (long long)m * H;
     // grid-stride over at most 4096 blocks: one published max per block
     const long long nb = std::min<long long>(nblocks(total, 256), 4096);
+    GM_RAN("k_lstm_pw_bwd");
     hipLaunchKernelGGL(k_lstm_pw_bwd, dim3((unsigned)nb), dim3(256), 0, st, dh1, dc1, act, c, c1, m, H, dgates, dc,
                        reinterpret_cast<unsigned*>(dgates_scale));
     int rc = launched();
@@ -1536,8 +1543,9 @@ extern "C" int gm_routing_node_encoder_bits(const float* x, int64_t ldx, const i
                                             int64_t ldy, uint32_t* sbits, int64_t ldsb, void* stream) {
     if (!x || !nbr || !wt || !y || G <= 0 || N < 4 || n <= 0 || (n % 64) || act < GM_ACT_NONE || act > GM_ACT_LAST ||
         ldx < 4 * N + 8 || ldy < n || (ldy % 2) || (reinterpret_cast<uintptr_t>(wt) & 15) ||
-        (sbits && ldsb < n / 32))
-        return gm_fail(GM_ERR_INVALID_ARG, "gm_routing_node_encoder: bad arguments (n % 64 == 0, 16-byte W^T)");
+        (reinterpret_cast<uintptr_t>(y) & 7) || (sbits && ldsb < n / 32))
+        return gm_fail(GM_ERR_INVALID_ARG,
+                       "gm_routing_node_encoder: bad arguments (n % 64 == 0, 16-byte W^T, 8-byte y, even ldy)");
     const int K = 4 * N + 8;
     // columns per lane: 2 while the block's W^T slice (K x 128 floats) fits 64 KB (N <= 30), else 1 (2 above
     // N = 30 with a slice of up to 160 KB at one block per CU measured within noise, round 4)
@@ -1553,6 +1561,7 @@ extern "C" int gm_routing_node_encoder_bits(const float* x, int64_t ldx, const i
     dim3 grid((unsigned)((M + rows - 1) / rows), (unsigned)(n / (64 * cpl)));
 #define GM_RENC(C, A)                                                                                               \
     do {                                                                                                            \
+        GM_RAN(lds > 65536 ? "k_routing_enc<" #C "," #A ">/lds>64K" : "k_routing_enc<" #C "," #A ">");              \
         if (lds > 65536)                                                                                            \
             (void)hipFuncSetAttribute((const void*)(k_routing_enc<C, A, 512>),                                      \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
@@ -1755,7 +1764,9 @@ __device__ __forceinline__ void lnlstm_row_bwd(const float* __restrict__ gi, con
         act[q][3] = sig_f(g[3]);
         cx[q] = cin[u];
         const float cp = act[q][1] * cx[q] + act[q][0] * act[q][2];
-        nc[q] = (cp - mc) * rc;
+        // one unit: the normalised value is 0 whatever c is (LayerNorm of a single element). Computed, it is the
+        // rounding of the recomputed cp against the saved mean times rc = 1 / sqrt(eps)
+        nc[q] = H == 1 ? 0.f : (cp - mc) * rc;
         const float cy = nc[q] * p.lc_w[u] + p.lc_b[u];
         const float th = tanh_f(cy);
         dcy[q] = gc1[q] + gh1[q] * act[q][3] * (1.f - th * th);
@@ -2154,8 +2165,11 @@ static int lnlstm_fwd(const char* name, const float* gi, int64_t ldgi, const flo
     const dim3 grid((m + 3) / 4), blk(256);
     hipStream_t st = (hipStream_t)stream;
 #define GM_LN(U)                                                                                                    \
-    hipLaunchKernelGGL(k_lnlstm_pw<U>, grid, blk, 0, st, gi, (long long)ldgi, gh, (long long)ldgh, c, (long long)ldc, \
-                       p, m, H, eps, h1, (long long)ldh, c1, (long long)ldc1, stats)
+    do {                                                                                                            \
+        g_last_lnlstm_pw = "k_lnlstm_pw<" #U ">";                                                                   \
+        hipLaunchKernelGGL(k_lnlstm_pw<U>, grid, blk, 0, st, gi, (long long)ldgi, gh, (long long)ldgh, c,           \
+                           (long long)ldc, p, m, H, eps, h1, (long long)ldh, c1, (long long)ldc1, stats);           \
+    } while (0)
     if (H <= 64)
         GM_LN(1);
     else if (H <= 128)
@@ -2208,9 +2222,12 @@ extern "C" int gm_lnlstm_bwd(const float* gi, int64_t ldgi, const float* gh, int
     const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
 #define GM_LNB(U)                                                                                                     \
-    hipLaunchKernelGGL(k_lnlstm_bwd<U>, grid, blk, 0, st, gi, (long long)ldgi, gh, (long long)ldgh, c, (long long)ldc, \
-                       p, stats, dh1, (long long)lddh, dc1, (long long)lddc, m, H, rows_per_wave, dgi,                 \
-                       (long long)lddgi, dgh, (long long)lddgh, dc, (long long)lddco, part)
+    do {                                                                                                              \
+        GM_RAN("k_lnlstm_bwd<" #U ">");                                                                               \
+        hipLaunchKernelGGL(k_lnlstm_bwd<U>, grid, blk, 0, st, gi, (long long)ldgi, gh, (long long)ldgh, c,            \
+                           (long long)ldc, p, stats, dh1, (long long)lddh, dc1, (long long)lddc, m, H, rows_per_wave, \
+                           dgi, (long long)lddgi, dgh, (long long)lddgh, dc, (long long)lddco, part);                 \
+    } while (0)
     if (H <= 64)
         GM_LNB(1);
     else if (H <= 128)
@@ -2272,6 +2289,7 @@ extern "C" int gm_gru_pointwise(const float* gi, int64_t ldgi, const float* gh, 
         ldh1 < H)
         return gm_fail(GM_ERR_INVALID_ARG, "gm_gru_pointwise: bad arguments (gate rows >= 3H)");
     const long long n = (long long)m * H;
+    GM_RAN("k_gru_pw");
     hipLaunchKernelGGL(k_gru_pw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi,
                        (long long)ldgi, gh, (long long)ldgh, h, (long long)ldh, m, H, h1, (long long)ldh1);
     hipError_t e = hipGetLastError();
@@ -2286,6 +2304,7 @@ extern "C" int gm_gru_bwd(const float* gi, int64_t ldgi, const float* gh, int64_
         ldgh < 3 * (int64_t)H || ldh < H || lddh1 < H || lddgi < 3 * (int64_t)H || lddgh < 3 * (int64_t)H || lddh < H)
         return gm_fail(GM_ERR_INVALID_ARG, "gm_gru_bwd: bad arguments (gate rows >= 3H)");
     const long long n = (long long)m * H;
+    GM_RAN("k_gru_bwd");
     hipLaunchKernelGGL(k_gru_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi,
                        (long long)ldgi, gh, (long long)ldgh, h, (long long)ldh, dh1, (long long)lddh1, m, H, dgi,
                        (long long)lddgi, dgh, (long long)lddgh, dh, (long long)lddh);

@@ -441,7 +441,10 @@ def concat_linears(owner, linears):
 
 def routing_encoder_ok(lin, N, Fd, nbr):
     """The routing node-obs layout (4N+8 columns, degree-3 neighbour table) lets the first
-    encoder layer run as a 12-column gather (gm_routing_node_encoder)."""
+    encoder layer run as a 12-column gather (gm_routing_node_encoder). Precondition, not checked (nbr is a
+    device table): three valid neighbours per node, every entry of nbr a node id in [0, N), as the 3-regular
+    routing topologies give; the kernel does not mask -1 entries. Shapes whose W^T slice needs more than 64 KB
+    of LDS are left to the dense GEMM here, though the C entry point takes them up to 160 KB."""
     return (Fd == 4 * N + 8 and nbr.shape[-1] == 3 and lin.out_features % 64 == 0 and
             (4 * N + 8) * 64 * (2 if lin.out_features % 128 == 0 and (4 * N + 8) <= 128 else 1) * 4 <= 65536)
 

@@ -613,8 +613,14 @@ int gm_gemm_pack_x3(const float* w, int64_t ldw, int32_t n, int32_t k, void* wp,
  * to src/env/routing.py:187-235): y = act(W x + b) from the 12 nonzero entries of each node
  * row (own one-hot, packet count and load, per neighbour one-hot, edge length, edge load)
  * instead of the dense K = 4N+8 product. x: node obs rows [G*N][ldx]; nbr int32 [G][N][3]
- * ascending; wt = W^T [4N+8][n] row-major (16-byte aligned); b [n] or NULL; y [G*N][ldy].
- * n % 64 == 0; act 0 none, 1 leaky_relu(0.01). */
+ * ascending; wt = W^T [4N+8][n] row-major (16-byte aligned); b [n] or NULL; y [G*N][ldy]
+ * (8-byte aligned, ldy even: n % 128 == 0 with 4N+8 <= 128 stores column pairs).
+ * n % 64 == 0; act: any GM_ACT_* (none and leaky_relu(0.01) have kernels of their own).
+ * Precondition: three valid neighbours per node, every nbr entry a node id in [0, N) (the
+ * routing graphs are 3-regular). A -1 entry is NOT masked here, unlike gm_mp_aggregate and
+ * gm_netmon_readout, and nbr is a device table, so the call cannot check it: such an entry
+ * would add the weight row before the neighbour's one-hot block.
+ * 4N+8 <= 640 (N <= 158, a 160 KB LDS slice); above: GM_ERR_UNSUPPORTED. */
 int gm_routing_node_encoder(const float* x, int64_t ldx, const int32_t* nbr, int32_t G, int32_t N,
                             const float* wt, const float* b, int32_t n, int32_t act, float* y, int64_t ldy,
                             void* stream);

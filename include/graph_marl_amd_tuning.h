@@ -47,6 +47,10 @@ const char* gm_gemm_form(void);
  * per call, nothing on the device; the tests of the dispatch thresholds read it
  * (tests/test_netmon_paths_gpu.py, tests/test_gemm_paths_gpu.py), the product never does. */
 const char* gm_last_kernel(void);
+/* The same for gm_lnlstm_fwd / gm_lnlstm_pointwise alone ("k_lnlstm_pw<1|2|4|8>", "" before the first call): a
+ * slot of its own, so that gm_last_kernel reads after those two calls what it read before they named a kernel
+ * (the recorded launch lists of the sequence-batched update depend on it). tests/test_encoder_cells_paths_gpu.py. */
+const char* gm_last_lnlstm_pw(void);
 /* The i-th kernel name the GEMM entry points of this build can report through gm_last_kernel, NULL past the
  * end: exactly the instantiations the two GEMM launchers were compiled for, plus the weight-gradient forms.
  * Filled when the library loads; needs no GPU. tests/test_gemm_paths_gpu.py requires a case for every name. */
