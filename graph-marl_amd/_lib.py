@@ -38,6 +38,7 @@ EXPORTS = [
     "gm_act_fwd", "gm_act_bwd_z", "gm_obs_from_gemm", "gm_encoder_x3", "gm_step_mse_blocks", "gm_step_mse",
     "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd", "gm_agent_comm_bwd",
     "gm_agent_attention_bwd", "gm_agent_attention_kl", "gm_netmon_global_rows", "gm_netmon_global_bwd",
+    "gm_aux_head_mse", "gm_aux_head_mse_bwd",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
@@ -222,6 +223,9 @@ def lib():
         "gm_agent_attention_kl": [vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp],
         "gm_netmon_global_rows": [vp, i64, i32, i32, i32, i32, vp, i64, vp],
         "gm_netmon_global_bwd": [vp, i64, i32, i32, i32, i32, vp, i64, vp],
+        "gm_aux_head_mse": [vp, i64, i64, i32, vp, i64, vp, i32, vp, i64, vp, i64, vp, i32, vp, vp, vp],
+        "gm_aux_head_mse_bwd": [vp, i64, i32, vp, i64, vp, i64, i32, i64, i32, C.c_float, vp, vp, i64, vp, vp, i32, vp,
+                                vp],
     }
     for name, at in newer.items():
         if hasattr(L, name) or not os.environ.get("GM_LIB"):

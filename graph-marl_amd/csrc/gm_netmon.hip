@@ -2482,3 +2482,238 @@ extern "C" int gm_step_mse_bwd(const float* pred, const float* tgt, int64_t n, i
                        L, g, two_over_n, reinterpret_cast<float4*>(grad));
     return launched();
 }
+
+// ---- NetMon aux head: its narrow second layer fused with the MSE (src/main.py:586-594, 868-875: MLP(S, [S, n_aux],
+// activation_on_output=False) on the new node state against get_node_aux, F.mse_loss) ----
+// Forward: res[r][a] = (b2[a] + sum_c y[r][c] w2[a][c]) - tgt[r][a], the c sum one fmaf chain in ascending c, so the
+// layer's [rows][n_out] output is never written and read back. A block owns rpb <= 64 rows and walks the K = cols
+// contraction in 32-column chunks staged in LDS (rows padded to 33 floats: lane a reads bank (a + c) % 32): lane
+// (rl, al) of the 8 x 32 block owns rows rl + 8 i and outputs al + 32 k, 8 x 4 accumulators with static indices.
+// Backward: g = s (res w2) (leaky mask of y from its sign bits) with 4 columns per thread as k_qhead_bwd4, the
+// block's res rows in LDS; W2's gradient s res^T y is a weight-gradient GEMM of the caller (gm_gemm_x3_wgrad).
+namespace {
+constexpr int AUX_RPB = 64;   // most rows per block (8 per row lane)
+constexpr int AUX_NMAX = 128;  // most outputs (4 per lane)
+constexpr int AUX_LD = 33;     // LDS row of a 32-column chunk
+
+__global__ __launch_bounds__(256) void k_aux_head_mse(const float* __restrict__ y, long long ldy, long long rows,
+                                                      int cols, const float* __restrict__ w2, long long ldw,
+                                                      const float* __restrict__ b2, int n_out,
+                                                      const float* __restrict__ tgt, long long ldt,
+                                                      float* __restrict__ res, long long ldr, float* __restrict__ part,
+                                                      int rpb, unsigned* __restrict__ amax,
+                                                      unsigned* __restrict__ y_amax) {
+    __shared__ float ys[AUX_RPB * AUX_LD];
+    __shared__ float ws[AUX_NMAX * AUX_LD];
+    __shared__ float wsum[4], wmx[4], wymx[4];
+    const int al = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const long long r0 = (long long)blockIdx.x * rpb;
+    const int nr = (int)min((long long)rpb, rows - r0);
+    const int NA = (n_out + 31) >> 5, RI = (rpb + 7) >> 3;
+    float acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc[i][k] = 0.f;
+    float ymx = 0.f;
+    for (int c0 = 0; c0 < cols; c0 += 32) {
+        for (int i = threadIdx.x; i < rpb * 8; i += 256) {
+            const int r = i >> 3, q = i & 7;
+            const float4 v = *reinterpret_cast<const float4*>(y + (r0 + min(r, nr - 1)) * ldy + c0 + 4 * q);
+            ymx = fmaxf(fmaxf(ymx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+            float* d = ys + r * AUX_LD + 4 * q;
+            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+        }
+        for (int i = threadIdx.x; i < n_out * 8; i += 256) {
+            const int a = i >> 3, q = i & 7;
+            const float4 v = *reinterpret_cast<const float4*>(w2 + a * ldw + c0 + 4 * q);
+            float* d = ws + a * AUX_LD + 4 * q;
+            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int c = 0; c < 32; c++) {
+            float w[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = k < NA ? ws[(al + 32 * k) * AUX_LD + c] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                if (i < RI) {
+                    const float yv = ys[(rl + 8 * i) * AUX_LD + c];
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k < NA) acc[i][k] = fmaf(yv, w[k], acc[i][k]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float sq = 0.f, mx = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int r = rl + 8 * i;
+        if (r < nr) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int a = al + 32 * k;
+                if (a < n_out) {
+                    const float v = (b2[a] + acc[i][k]) - tgt[(r0 + r) * ldt + a];
+                    res[(r0 + r) * ldr + a] = v;
+                    sq = fmaf(v, v, sq);
+                    mx = fmaxf(mx, fabsf(v));
+                }
+            }
+        }
+    }
+    // the block's sum in a fixed order: lane sums, the wave's xor tree, then (w0 + w1) + (w2 + w3)
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    mx = gm_wave_max(mx);
+    ymx = gm_wave_max(ymx);
+    if ((threadIdx.x & 63) == 0) {
+        wsum[threadIdx.x >> 6] = sq;
+        wmx[threadIdx.x >> 6] = mx;
+        wymx[threadIdx.x >> 6] = ymx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        if (amax) gm_amax_publish(amax, fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3])));
+        if (y_amax) gm_amax_publish(y_amax, fmaxf(fmaxf(wymx[0], wymx[1]), fmaxf(wymx[2], wymx[3])));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_aux_head_mse_bwd(const float* __restrict__ res, long long ldr, int n_out,
+                                                          const float* __restrict__ w2, long long ldw,
+                                                          const unsigned* __restrict__ bits, long long ldm,
+                                                          long long rows, int cols, float scale,
+                                                          const float* __restrict__ scale_dev, float* __restrict__ g,
+                                                          long long ldg, float* __restrict__ part_b1,
+                                                          float* __restrict__ part_b2, int rpb,
+                                                          unsigned* __restrict__ amax) {
+    __shared__ float rs[AUX_RPB * AUX_NMAX];  // the block's res rows, [row][n_out]
+    __shared__ float4 red[256];
+    __shared__ float wmx[4];
+    const float s = scale * (scale_dev ? *scale_dev : 1.f);
+    const long long r0 = (long long)blockIdx.x * rpb;
+    const int nr = (int)min((long long)rpb, rows - r0);
+    for (int i = threadIdx.x; i < nr * n_out; i += 256) rs[i] = res[(r0 + i / n_out) * ldr + i % n_out];
+    __syncthreads();
+    const int C4 = cols >> 2, RL = 256 / C4;
+    const bool active = (int)threadIdx.x < RL * C4;
+    const int c4 = threadIdx.x % C4, rl = threadIdx.x / C4, c = 4 * c4;
+    float4 pb = make_float4(0.f, 0.f, 0.f, 0.f);
+    float mx = 0.f;
+    constexpr int U = 4;
+    if (active) {
+        for (int rb = rl; rb < nr; rb += U * RL) {
+            float4 acc[U];
+            int ro[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                ro[u] = min(rb + u * RL, nr - 1) * n_out;
+            }
+            for (int a = 0; a < n_out; a++) {
+                const float4 w = *reinterpret_cast<const float4*>(w2 + a * ldw + c);
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const float rv = rs[ro[u] + a];
+                    acc[u].x = fmaf(rv, w.x, acc[u].x);
+                    acc[u].y = fmaf(rv, w.y, acc[u].y);
+                    acc[u].z = fmaf(rv, w.z, acc[u].z);
+                    acc[u].w = fmaf(rv, w.w, acc[u].w);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int r = rb + u * RL;
+                if (r >= nr) break;
+                float4 v = make_float4(s * acc[u].x, s * acc[u].y, s * acc[u].z, s * acc[u].w);
+                if (bits) {  // bit set: y > 0; clear: the leaky slope
+                    const unsigned m = bits[(r0 + r) * ldm + (c >> 5)] >> (c & 31);
+                    if (!(m & 1u)) v.x *= 0.01f;
+                    if (!(m & 2u)) v.y *= 0.01f;
+                    if (!(m & 4u)) v.z *= 0.01f;
+                    if (!(m & 8u)) v.w *= 0.01f;
+                }
+                *reinterpret_cast<float4*>(g + (r0 + r) * ldg + c) = v;
+                pb.x += v.x;
+                pb.y += v.y;
+                pb.z += v.z;
+                pb.w += v.w;
+                mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+            }
+        }
+    }
+    red[threadIdx.x] = pb;
+    mx = gm_wave_max(mx);
+    if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if ((int)threadIdx.x < C4) {  // the row lanes' column sums in lane order
+        float4 sm = red[threadIdx.x];
+        for (int l = 1; l < RL; l++) {
+            const float4 o = red[l * C4 + threadIdx.x];
+            sm.x += o.x;
+            sm.y += o.y;
+            sm.z += o.z;
+            sm.w += o.w;
+        }
+        *reinterpret_cast<float4*>(part_b1 + (long long)blockIdx.x * cols + c) = sm;
+    }
+    if ((int)threadIdx.x < n_out) {
+        float sm = 0.f;
+        for (int r = 0; r < nr; r++) sm += rs[r * n_out + threadIdx.x];
+        part_b2[(long long)blockIdx.x * n_out + threadIdx.x] = s * sm;
+    }
+    if (amax && threadIdx.x == 0) gm_amax_publish(amax, fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3])));
+}
+
+bool aux_a16(const void* p, long long ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0; }
+bool aux_a4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+}  // namespace
+
+extern "C" int gm_aux_head_mse(const float* y, int64_t ldy, int64_t rows, int32_t cols, const float* w2, int64_t ldw,
+                               const float* b2, int32_t n_out, const float* tgt, int64_t ldt, float* res, int64_t ldr,
+                               float* part, int32_t rows_per_block, float* res_amax, float* y_amax, void* stream) {
+    if (!y || !w2 || !b2 || !tgt || !res || !part || rows <= 0 || cols < 32 || cols > 1024 || cols % 32 || n_out < 1 ||
+        n_out > AUX_NMAX || rows_per_block < 8 || rows_per_block > AUX_RPB || rows_per_block % 8 || ldy < cols ||
+        ldw < cols || ldt < n_out || ldr < n_out || !aux_a16(y, ldy) || !aux_a16(w2, ldw) || !aux_a4(b2) ||
+        !aux_a4(tgt) || !aux_a4(res) || !aux_a4(part) || !aux_a4(res_amax) || !aux_a4(y_amax) ||
+        (rows + rows_per_block - 1) / rows_per_block > 0x7fffffffll)
+        return gm_fail(GM_ERR_INVALID_ARG,
+                       "gm_aux_head_mse: bad arguments (cols % 32 == 0, cols <= 1024, 1 <= n_out <= 128, rows_per_block "
+                       "a multiple of 8 up to 64, y / w2 rows 16-byte aligned)");
+    const long long nb = (rows + rows_per_block - 1) / rows_per_block;
+    GM_RAN("k_aux_head_mse");
+    hipLaunchKernelGGL(k_aux_head_mse, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, y, (long long)ldy,
+                       (long long)rows, cols, w2, (long long)ldw, b2, n_out, tgt, (long long)ldt, res, (long long)ldr,
+                       part, rows_per_block, reinterpret_cast<unsigned*>(res_amax),
+                       reinterpret_cast<unsigned*>(y_amax));
+    return launched();
+}
+
+extern "C" int gm_aux_head_mse_bwd(const float* res, int64_t ldr, int32_t n_out, const float* w2, int64_t ldw,
+                                   const uint32_t* mask_bits, int64_t ldm, int32_t act, int64_t rows, int32_t cols,
+                                   float scale, const float* scale_dev, float* g, int64_t ldg, float* part_b1,
+                                   float* part_b2, int32_t rows_per_block, float* g_scale, void* stream) {
+    if (!res || !w2 || !g || !part_b1 || !part_b2 || rows <= 0 || cols < 32 || cols > 1024 || cols % 32 || n_out < 1 ||
+        n_out > AUX_NMAX || rows_per_block < 1 || rows_per_block > AUX_RPB || ldr < n_out || ldw < cols || ldg < cols ||
+        (act != 0 && act != 1) || (act == 1 && (!mask_bits || ldm < cols / 32 || !aux_a4(mask_bits))) ||
+        !aux_a4(res) || !aux_a16(w2, ldw) || !aux_a16(g, ldg) || !aux_a16(part_b1, 4) || !aux_a4(part_b2) ||
+        !aux_a4(scale_dev) || !aux_a4(g_scale) || (rows + rows_per_block - 1) / rows_per_block > 0x7fffffffll)
+        return gm_fail(GM_ERR_INVALID_ARG,
+                       "gm_aux_head_mse_bwd: bad arguments (cols % 32 == 0, cols <= 1024, 1 <= n_out <= 128, "
+                       "rows_per_block <= 64, act 0 / 1 with mask_bits, w2 / g rows and part_b1 16-byte aligned)");
+    hipStream_t st = (hipStream_t)stream;
+    if (g_scale && hipMemsetAsync(g_scale, 0, sizeof(float), st) != hipSuccess)
+        return gm_fail(GM_ERR_HIP, "gm_aux_head_mse_bwd: memset");
+    const long long nb = (rows + rows_per_block - 1) / rows_per_block;
+    GM_RAN("k_aux_head_mse_bwd");
+    hipLaunchKernelGGL(k_aux_head_mse_bwd, dim3((unsigned)nb), dim3(256), 0, st, res, (long long)ldr, n_out, w2,
+                       (long long)ldw, act ? mask_bits : nullptr, (long long)ldm, (long long)rows, cols, scale,
+                       scale_dev, g, (long long)ldg, part_b1, part_b2, rows_per_block,
+                       reinterpret_cast<unsigned*>(g_scale));
+    int rc = launched();
+    if (rc == GM_OK && g_scale) rc = gm_absmax_finish(g_scale, stream);
+    return rc;
+}

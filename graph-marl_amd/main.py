@@ -481,7 +481,9 @@ def _main(args, rank, world):
                 loss, q_all, qt_all = TS.dqn_update_seq(netmon, model, model_tar, optimizer, params,
                                                         buff.get_sequences(args.mini_batch_size,
                                                                            args.sequence_length),
-                                                        args.gamma, args.tau, args.target_update_steps, iteration)
+                                                        args.gamma, args.tau, args.target_update_steps, iteration,
+                                                        aux_model=aux_model, aux_coeff=args.aux_loss_coeff,
+                                                        parts=parts)
                 qs, qts = list(q_all), list(qt_all)
             elif args.sequence_length > 1 and AS.agent_seq_ok(model, model_tar, netmon, att, aux_model, n_agents):
                 # DQNR / CommNet without NetMon: the sequence-batched update of agent_seq.py

@@ -229,7 +229,8 @@ class ReplayBuffer:
                         self.reward[slots, envs].to(fl), self.done[slots, envs], self.episode_done[slots],
                         self._records(self.node_obs, slots, env), self.nbr[slots, envs].int().contiguous(),
                         self.agent_node[slots, envs].int().contiguous(), self._records(self.node_state, first, env),
-                        next_fields, (slots, env))
+                        next_fields, (slots, env),
+                        self.node_aux[slots, envs].to(fl).contiguous() if self.node_aux is not None else None)
 
     def get_agent_sequences(self, batch_size, sequence_length):
         """The sequences get_batch(batch_size, sequence_length) draws (same stream, same indices), as one

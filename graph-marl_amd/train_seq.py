@@ -32,9 +32,21 @@ is one autograd node over the whole sequence (`_SeqFn`), organised for the GPU:
 
 Every GEMM runs in the split-f16 form with fp32 accumulation (gm_gemm_x3 / gm_gemm_x3_wgrad),
 as in the autograd path (train.dqn_loss), which remains the path for every other configuration
-(no carry-over, aux loss, GM_GEMM=f32; DQNR / CommNet without NetMon: agent_seq.py, with NetMon:
+(no carry-over, an aux head aux_ok refuses, GM_GEMM=f32; DQNR / CommNet without NetMon: agent_seq.py, with NetMon:
 agent_netmon_seq.py; DGN without NetMon: dgn_seq.py; DGN with NetMon: dgn_netmon_seq.py, which runs the NetMon half of this
 module, _forward_netmon / _backward_netmon, around the DGN half of dgn_seq.py).
+
+Aux loss (--aux-loss-coeff, src/main.py:586-594, 868-875, 996-1000; seq_loss(aux_model=...)): the head MLP(S, [S,
+n_aux]) runs once over S[K] of all L steps viewed as [L*B*N, S] (the state after each step, before the episode mask)
+against SeqBatch.node_aux, and the node returns loss_aux = sum res^2 / (L*B*N*n_aux) as a second output (_forward_aux).
+Layer 1 is a batched leaky GEMM with sign bits like the encoder's; layer 2, the residual and the squared sum are
+gm_aux_head_mse in fp32 (no GEMM tile is n_aux = 20 columns wide, and the layer's output would be written and read
+back). Backward (_backward_aux): gm_aux_head_mse_bwd gives layer 1's output gradient (leaky mask, 2 * upstream /
+(L*B*N*n_aux) folded in), both bias partials and the gradient's scale; W2's gradient res^T y is _wgrad on the two
+operand scales the forward kernel published; layer 1's input gradient [dh_aux | dc_aux] is one _dgrad split at H: dh_aux
+is added onto dh_final before the cell loop, dc_aux[t] is the dc source of step t's last update cell (gm_lstm_bwd_args.dc
+/ gm_lnlstm_cell_bwd_args.dc, unused at j == K otherwise; gru has no c). Without an aux model nothing of this is
+launched or allocated.
 
 Global readout (NetMon output_global_hidden, --netmon-global; graph observation [h | global | nbr x 3] with
 global = the mean of h over the graph's nodes, src/model.py:458-469): the readout buffer is [L*B*A, 5H] =
@@ -55,13 +67,14 @@ from . import fused as FU
 from . import model as MD
 
 SeqBatch = namedtuple("SeqBatch", ["obs", "obs_dim", "action", "reward", "done", "episode_done", "node_obs", "nbr",
-                                   "agent_node", "node_state", "next_fields", "idx"], defaults=(None,))
+                                   "agent_node", "node_state", "next_fields", "idx", "node_aux"],
+                      defaults=(None, None))
 """All L steps of B replay sequences, stacked: obs [L, B, A, odp] (rows padded to 16 bytes, first
 obs_dim columns valid), action [L, B, A] long, reward [L, B, A], done [L, B, A] bool, episode_done
 [L, B] bool, node_obs [L, B, N, F], nbr [L, B, N, deg] int32, agent_node [L, B, A] int32,
 node_state [B, N, state_size] (the NetMon state before step 0: [h | c], gru: h). next_fields(t, rows) -> (next_obs
 [len, A, odp], next_node_obs [len, N, F], next_agent_node [len, A] int32) of step t for the
-sequences `rows` (None = all)."""
+sequences `rows` (None = all). node_aux [L, B, N, n_aux] (the aux head's targets) when the ring stores them."""
 
 
 def cell_ok(netmon):
@@ -82,11 +95,24 @@ def netmon_seq_ok(netmon):
             and all(l.act == 1 and l.bias is not None for l in enc))
 
 
+def aux_ok(netmon, aux_model):
+    """The aux head _forward_aux takes (main.py's MLP(S, [S, n_aux], activation_on_output=False) on the NetMon state
+    row of S floats): exactly two Linear layers with biases, the first leaky and S -> S, the second without
+    activation, S <= 1024 and n_aux <= 128 (gm_aux_head_mse)."""
+    ll = list(getattr(aux_model, "linear_layers", []))
+    S = netmon.state_size
+    return (type(aux_model) is MD.MLP and len(ll) == 2 and all(l.bias is not None for l in ll)
+            and ll[0].act == 1 and ll[1].act == 0 and ll[0].in_features == S and ll[0].out_features == S
+            and ll[1].in_features == S and S <= 1024 and S % 32 == 0 and 1 <= ll[1].out_features <= 128)
+
+
 def seq_ok(netmon, model, model_tar, att_coeff=0.0, aux_model=None):
     """The sequence-batched path covers the reference's NetMon + DQN configuration: LSTM, GRU or LayerNorm-LSTM
     cells with carry-over, sum / mean aggregation, neighbour readout (with or without the global mean), leaky MLPs,
-    split-f16 GEMMs."""
-    if netmon is None or aux_model is not None or att_coeff != 0 or L.GEMM_MODE != "x3":
+    split-f16 GEMMs, with or without the aux loss on a head aux_ok takes."""
+    if netmon is None or att_coeff != 0 or L.GEMM_MODE != "x3":
+        return False
+    if aux_model is not None and not aux_ok(netmon, aux_model):
         return False
     if type(model) is not MD.DQN or type(model_tar) is not MD.DQN:
         return False
@@ -504,6 +530,68 @@ def _wgrad(g, sa, x, k, sb_):
     return MD._wgrad(g, x, k, sa, sb_)
 
 
+AUX_RPB = 64  # rows per block of gm_aux_head_mse / gm_aux_head_mse_bwd
+
+
+def _forward_aux(p):
+    """The NetMon aux loss (src/main.py:586-594, 868-875) after _forward_netmon: the head p.aux once over S[K] of all
+    steps viewed as [L*B*N, S] (the state after each step, before the episode mask) against seq.node_aux. Layer 1
+    is a batched leaky GEMM like the encoder's; layer 2, the residual and the squared sum are gm_aux_head_mse.
+    Returns sum res^2 / (L*B*N*n_aux) = the reference's sum_t mean_t / L (every step has the same row count)."""
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
+    l1, l2 = p.aux.linear_layers
+    SK = p.S[K]
+    S2 = SK.shape[-1]
+    LM = Ls * M
+    dev = SK.device
+    na = l2.out_features
+    tgt = p.seq.node_aux.reshape(LM, na).to(torch.float32).contiguous()
+    y = torch.empty(LM, S2, device=dev)
+    yb = _sign_bits(LM, S2, dev)
+    sx = _zeros1(dev)
+    _gemm_amax(SK, S2, S2, _lin_x3(l1), l1.bias, LM, S2, FU.GM_EPI_BIAS_LEAKY, y, S2, sx, sbits=yb)
+    _finish(sx)
+    res = torch.empty(LM, na, device=dev)
+    part = torch.empty((LM + AUX_RPB - 1) // AUX_RPB, device=dev)
+    sr, sy = _zeros1(dev), _zeros1(dev)  # max |res|, max |y|: the operand scales of W2's gradient GEMM
+    w2 = l2.weight.detach()
+    L.check(L.lib().gm_aux_head_mse(y.data_ptr(), S2, LM, S2, w2.data_ptr(), w2.stride(0), l2.bias.data_ptr(), na,
+                                    tgt.data_ptr(), na, res.data_ptr(), na, part.data_ptr(), AUX_RPB, sr.data_ptr(),
+                                    sy.data_ptr(), L.stream_ptr()))
+    p.aux_saved = (y, yb, sx, res, _finish(sr), _finish(sy))
+    return part.sum() / (LM * na)
+
+
+def _backward_aux(p, daux, grads):
+    """Backward of _forward_aux from daux, the upstream gradient of its loss (it carries aux_coeff): the head's
+    parameter gradients into grads; returns the gradient of S[K] of all steps as (dh_aux [L*B*N, H], dc_aux (the
+    same shape; gru: None)), layer 1's input gradient in one GEMM split at H."""
+    Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
+    l1, l2 = p.aux.linear_layers
+    y, yb, sx, res, sr, sy = p.aux_saved
+    LM, S2 = y.shape
+    na = l2.out_features
+    dev = y.device
+    nb = (LM + AUX_RPB - 1) // AUX_RPB
+    g = torch.empty(LM, S2, device=dev)
+    pb1, pb2 = torch.empty(nb, S2, device=dev), torch.empty(nb, na, device=dev)
+    sc = torch.empty(1, device=dev)
+    up = daux.detach().reshape(1).to(torch.float32).contiguous()
+    scale = 2.0 / (LM * na)
+    w2 = l2.weight.detach()
+    L.check(L.lib().gm_aux_head_mse_bwd(res.data_ptr(), na, na, w2.data_ptr(), w2.stride(0), yb.data_ptr(),
+                                        yb.stride(0), 1, LM, S2, scale, up.data_ptr(), g.data_ptr(), S2,
+                                        pb1.data_ptr(), pb2.data_ptr(), AUX_RPB, sc.data_ptr(), L.stream_ptr()))
+    grads[l2.weight] = _wgrad(res, sr, y, S2, sy) * (up * scale)
+    grads[l2.bias] = pb2.sum(0)
+    grads[l1.bias] = pb1.sum(0)
+    grads[l1.weight] = _wgrad(g, sc, p.S[K].view(LM, S2), S2, sx)
+    dh = torch.empty(LM, H, device=dev)
+    dc = torch.empty(LM, H, device=dev) if S2 > H else None
+    _dgrad(g, S2, S2, sc, _lin_x3t(l1), LM, S2, H, None, 0, dh, H, dc, H)
+    return dh, dc
+
+
 def _gru_cells_bwd(p, dhf, dhp, grads):
     """GRU cells of _backward, per step and cell in reverse: gm_gru_cell_bwd (sums the cell's gradient sources,
     writes the gate gradients dG and the direct h gradient g z), then one input-gradient GEMM on W4^T giving
@@ -587,13 +675,14 @@ def _gru_cells_bwd(p, dhf, dhp, grads):
     return gE, partE, gmaxE
 
 
-def _lnlstm_cells_bwd(p, dhf, dhp, grads):
+def _lnlstm_cells_bwd(p, dhf, dhp, grads, dc_aux=None):
     """LayerNorm-LSTM cells of _backward, per step and cell in reverse: gm_lnlstm_cell_bwd (sums the cell's gradient
     sources; writes dgi, dgh, the c gradient, parameter partials, the two scales and maxima), then the input
     gradients dgh @ W_hh (h part) and, for the update cell, dgi @ W_ih (the previous cell's transposed-aggregate
     source). The obs cell's dgi of all steps goes through W_ih and the encoder's last leaky mask in ONE GEMM after
-    the loop, on the scale finished from the accumulated max. Fills the cells' parameter gradients; returns (gE,
-    partE, gmaxE) for the batched encoder backward."""
+    the loop, on the scale finished from the accumulated max. dc_aux [L*M, H] (optional): the aux head's gradient of
+    every step's final c, the dc source of the step's last update cell. Fills the cells' parameter gradients; returns
+    (gE, partE, gmaxE) for the batched encoder backward."""
     netmon = p.netmon
     Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
     S2 = 2 * H
@@ -643,6 +732,8 @@ def _lnlstm_cells_bwd(p, dhf, dhp, grads):
                 a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
                 a.dc_ext, a.ld_dcext = dc_ext.data_ptr(), H
                 a.ext_mask, a.rows_per_sample = ep_done[t].data_ptr(), N
+            if j == K and dc_aux is not None:
+                dc_next = dc_aux[t * M:(t + 1) * M]
             if dc_next is not None:
                 a.dc, a.ld_dc = dc_next.data_ptr(), H
             a.dgi, a.ld_dgi, a.dgh, a.ld_dgh = dgi.data_ptr(), 4 * H, dgh.data_ptr(), 4 * H
@@ -686,7 +777,7 @@ def _lnlstm_cells_bwd(p, dhf, dhp, grads):
     return gE, partE, gmaxE
 
 
-def _backward(p, dq):
+def _backward(p, dq, daux=None):
     dqn = p.dqn
     Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
     dev = dq.device
@@ -739,13 +830,14 @@ def _backward(p, dq):
     dR = torch.empty(LMa, GW, device=dev)
     _dgrad(g, lin0.out_features, lin0.out_features, sc, _dqn_first_x3t(lin0, od, H, glob), LMa, GW, GW,
            None, 0, dR, GW)
-    return _backward_netmon(p, dR, grads)
+    return _backward_netmon(p, dR, grads, daux)
 
 
-def _backward_netmon(p, dR, grads):
+def _backward_netmon(p, dR, grads, daux=None):
     """The NetMon half of the backward from dR [L*B*A, GW], the gradient of the readout buffer p.R: the readout's
-    transpose, the cells per step in reverse, the batched encoder backward. Adds NetMon's parameter gradients to
-    grads and returns it."""
+    transpose, the cells per step in reverse, the batched encoder backward. daux (with p.aux): the upstream
+    gradient of _forward_aux's loss, whose state gradient joins the readout's before the cell loop. Adds NetMon's
+    (and the aux head's) parameter gradients to grads and returns it."""
     netmon = p.netmon
     Ls, B, A, N, F, od, odp, H, K, M, Ma = p.dims
     S2 = 2 * H  # (lstm branch)
@@ -763,12 +855,16 @@ def _backward_netmon(p, dR, grads):
         with L.timed(f"gm_netmon_global_bwd:{LM}x{H}"):
             L.check(lib.gm_netmon_global_bwd(dR.data_ptr() + 16 * H, GW, Ls * B, N, H, A, dhf.data_ptr(), H,
                                              L.stream_ptr()))
+    dc_aux = None
+    if daux is not None:  # [dh_aux | dc_aux] of S[K] of all steps: h joins dh_final, c the last update cell's dc
+        dh_aux, dc_aux = _backward_aux(p, daux, grads)
+        dhf.add_(dh_aux)
 
     # ---- recurrent cells, per step, in reverse ----
     if netmon.rnn_type == "gru":
         gE, partE, gmaxE = _gru_cells_bwd(p, dhf, dhp, grads)
     elif netmon.rnn_type == "lnlstm":
-        gE, partE, gmaxE = _lnlstm_cells_bwd(p, dhf, dhp, grads)
+        gE, partE, gmaxE = _lnlstm_cells_bwd(p, dhf, dhp, grads, dc_aux)
     else:
         dG = torch.empty(K + 1, Ls, M, 4 * H, device=dev)
         rpb_c = 64
@@ -814,6 +910,8 @@ def _backward_netmon(p, dR, grads):
                     a.dh_ext, a.ld_ext = dh_ext.data_ptr(), H
                     a.dc_ext, a.ld_dcext = dc_ext.data_ptr(), H
                     a.ext_mask, a.rows_per_sample = ep_done[t].data_ptr(), N
+                if j == K and dc_aux is not None:  # the aux head's gradient of this step's final c
+                    dc_next = dc_aux[t * M:(t + 1) * M]
                 if dc_next is not None:
                     a.dc, a.ld_dc = dc_next.data_ptr(), H
                 a.m, a.hidden = M, H
@@ -874,12 +972,15 @@ class _SeqFn(torch.autograd.Function):
     def forward(ctx, plan, *params):
         ctx.plan = plan
         with torch.no_grad():
-            return _forward(plan)
+            q = _forward(plan)
+            if plan.aux is None:
+                return q
+            return q, _forward_aux(plan)
 
     @staticmethod
-    def backward(ctx, dq):
+    def backward(ctx, dq, daux=None):
         p = ctx.plan
-        grads = _backward(p, dq)
+        grads = _backward(p, dq, daux)
         ctx.plan = None
         return (None,) + tuple(grads.get(w) for w in p.params)
 
@@ -917,29 +1018,43 @@ def _target_max(p, model_tar, gamma_unused=None):
     return out
 
 
-def seq_loss(netmon, model, model_tar, seq, gamma, params, parts=None):
-    """TD loss of src/main.py:840-1000 over a SeqBatch: (loss, q [L, B, A, nq], q_target)."""
+def seq_loss(netmon, model, model_tar, seq, gamma, params, parts=None, aux_model=None, aux_coeff=0.0):
+    """Loss of src/main.py:840-1000 over a SeqBatch: (loss, q [L, B, A, nq], q_target). aux_model (aux_ok): the
+    NetMon aux loss against seq.node_aux, weighted by aux_coeff, is added (params then includes the head's);
+    parts (a dict) receives the loss terms."""
     p = _Plan()
-    p.netmon, p.dqn, p.seq, p.params = netmon, model, seq, list(params)
-    q = _SeqFn.apply(p, *p.params)
+    p.netmon, p.dqn, p.seq, p.params, p.aux = netmon, model, seq, list(params), aux_model
+    loss_aux = None
+    if aux_model is None:
+        q = _SeqFn.apply(p, *p.params)
+    else:
+        if seq.node_aux is None:
+            raise ValueError("seq_loss: the aux loss needs SeqBatch.node_aux (ReplayBuffer(node_aux_size=...))")
+        want = (*seq.node_obs.shape[:3], aux_model.linear_layers[-1].out_features)
+        if tuple(seq.node_aux.shape) != want:
+            raise ValueError(f"seq_loss: SeqBatch.node_aux is {tuple(seq.node_aux.shape)}, the aux head wants {want} "
+                             "([L, B, N, n_aux])")
+        q, loss_aux = _SeqFn.apply(p, *p.params)
     Ls, B, A = seq.action.shape
     q = q.view(Ls, B, A, -1)
     nxt = _target_max(p, model_tar)
     target = seq.reward + (~seq.done) * gamma * nxt
     q_target = torch.scatter(q.detach(), -1, seq.action.unsqueeze(-1), target.unsqueeze(-1))
-    loss = (q - q_target).pow(2).mean(dim=(1, 2, 3)).sum() / Ls
+    loss_q = (q - q_target).pow(2).mean(dim=(1, 2, 3)).sum() / Ls
+    loss = loss_q if loss_aux is None else loss_q + aux_coeff * loss_aux
     if parts is not None:
-        parts.update(loss_q=loss, loss_att=None, loss_aux=None)
+        parts.update(loss_q=loss_q, loss_att=None, loss_aux=loss_aux)
     return loss, q, q_target
 
 
 def dqn_update_seq(netmon, model, model_tar, optimizer, params, seq, gamma, tau, target_update_steps=0, iteration=1,
-                   group=None):
+                   group=None, aux_model=None, aux_coeff=0.0, parts=None):
     """One update (src/main.py:840-1026) on a SeqBatch: the sequence-batched loss and backward, the
-    gradient all-reduce across ranks, clip by value (0.5) and norm (1.0), AdamW, target update."""
+    gradient all-reduce across ranks, clip by value (0.5) and norm (1.0), AdamW, target update. params must
+    include aux_model's parameters when the aux loss is on (src/main.py:594)."""
     from .train import allreduce_gradients, interpolate_model
 
-    loss, q, qt = seq_loss(netmon, model, model_tar, seq, gamma, params)
+    loss, q, qt = seq_loss(netmon, model, model_tar, seq, gamma, params, parts, aux_model, aux_coeff)
     optimizer.zero_grad(set_to_none=False)
     loss.backward()
     allreduce_gradients(params, group)

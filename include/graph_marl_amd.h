@@ -437,6 +437,36 @@ int gm_lnlstm_cell_bwd(const gm_lnlstm_cell_bwd_args* a, void* stream);
 int gm_qhead_bwd(const float* dq, int64_t ldq, int32_t nq, const float* wq, int64_t ldwq, const float* y,
                  int64_t ldy, int64_t rows, int32_t cols, int32_t act, float* g, int64_t ldg, float* part_b,
                  float* part_wq, float* part_bq, int32_t rows_per_block, float* g_scale, void* stream);
+/* NetMon aux head (src/main.py:586-594, 868-875: MLP(S, [S, n_aux], activation_on_output=False) on the new node
+ * state, F.mse_loss against get_node_aux): its narrow second layer fused with the loss, in fp32 as the Q head.
+ * gm_aux_head_mse: for r < rows, a < n_out
+ *   res[r][a] = (b2[a] + sum_c y[r][c] w2[a][c]) - tgt[r][a]
+ * with the c sum one fp32 fmaf chain in ascending c; y [rows][ldy] (the leaky first layer's output), w2 [n_out][ldw],
+ * tgt [rows][ldt], res [rows][ldr] (columns >= n_out untouched). part[blk] = the sum of res^2 over the block of
+ * rows_per_block rows, in an order fixed by (rows_per_block, n_out): the caller sums the ceil(rows /
+ * rows_per_block) partials in order and divides by rows * n_out. res_amax / y_amax (nullable): max |res| / max |y|
+ * accumulated as float bits by atomicMax into a slot the caller zeroed (gm_absmax_finish turns each into the
+ * power-of-two operand scale of gm_absmax_scale, so the weight-gradient GEMM res^T y needs no extra pass).
+ * cols % 32 == 0, 32 <= cols <= 1024, 1 <= n_out <= 128, rows_per_block a multiple of 8 up to 64; y and w2: 16-byte
+ * base and ld % 4 == 0; the others 4-byte aligned with ld >= n_out. Anything else: GM_ERR_INVALID_ARG, nothing
+ * launched. One launch.
+ * gm_aux_head_mse_bwd: with s = scale * (scale_dev ? *scale_dev : 1) (scale_dev: one device float, e.g. the
+ * upstream gradient of the loss; nullable)
+ *   g[r][c] = s * (sum_a res[r][a] w2[a][c]) * (act && y[r][c] <= 0 ? 0.01 : 1)
+ * the a sum in ascending a, y's sign from mask_bits [rows][ldm] uint32 words (bit c % 32 of word c / 32 set when
+ * y > 0, as gm_gemm_x3's act_out writes them; act 0: no mask, mask_bits unused); per block of rows_per_block
+ * (1..64) rows part_b1[blk][c] = sum_r g (the first layer's bias gradient) and part_b2[blk][a] = s * sum_r res
+ * (the second's), in a fixed order; g_scale (nullable): the power-of-two scale of g (gm_absmax_scale semantics,
+ * as gm_qhead_bwd). The second layer's weight gradient is s * res^T y: gm_gemm_x3_wgrad on res and y (n_out % 4
+ * == 0) with the two scales gm_aux_head_mse published. The same limits on cols and n_out; w2, g: 16-byte base
+ * and ld % 4 == 0, part_b1 16-byte base. Anything else: GM_ERR_INVALID_ARG, nothing launched or written. */
+int gm_aux_head_mse(const float* y, int64_t ldy, int64_t rows, int32_t cols, const float* w2, int64_t ldw,
+                    const float* b2, int32_t n_out, const float* tgt, int64_t ldt, float* res, int64_t ldr,
+                    float* part, int32_t rows_per_block, float* res_amax, float* y_amax, void* stream);
+int gm_aux_head_mse_bwd(const float* res, int64_t ldr, int32_t n_out, const float* w2, int64_t ldw,
+                        const uint32_t* mask_bits, int64_t ldm, int32_t act, int64_t rows, int32_t cols, float scale,
+                        const float* scale_dev, float* g, int64_t ldg, float* part_b1, float* part_b2,
+                        int32_t rows_per_block, float* g_scale, void* stream);
 /* gm_netmon_readout with strided h rows (h_final [.][ldf], h_prev [.][ldp]; e.g. the [h | c]
  * state rows of the LSTM, ld = 2H). */
 int gm_netmon_readout_ld(const float* h_final, int64_t ldf, const float* h_prev, int64_t ldp, const int32_t* nbr,
