@@ -394,9 +394,10 @@ def linear_rows(lin, x, ldx, M, out, ldo, k=None):
     return out
 
 
-def mlp_rows(mlp, x, ldx, k, M, scratch, out=None, ldo=None):
+def mlp_rows(mlp, x, ldx, k, M, scratch, out=None, ldo=None, start=0):
     """MLP over strided rows; the last layer writes into `out` (stride ldo) when given.
-    Rows whose stride or base is not 16-byte aligned are first copied into a padded buffer."""
+    Rows whose stride or base is not 16-byte aligned are first copied into a padded buffer.
+    start = 1: x holds the first layer's output (agent_first_layer) and the remaining layers run."""
     if ldx % 4 or x.data_ptr() % 16:
         xp = scratch(("mlp_in", id(mlp)), M, (k + 3) // 4 * 4)
         xp[:, :k].copy_(torch.as_strided(x, (M, k), (ldx, 1)))
@@ -404,6 +405,8 @@ def mlp_rows(mlp, x, ldx, k, M, scratch, out=None, ldo=None):
     h, ld, kk = x, ldx, k
     layers = list(mlp.linear_layers)
     for i, lin in enumerate(layers):
+        if i < start:
+            continue
         if i == len(layers) - 1 and out is not None:
             dst, ldd = out, ldo
         else:
@@ -585,6 +588,57 @@ def netmon_step(netmon, node_obs, nbr, state, out=None, last_out=None):
     return netmon.state, last
 
 
+def first_layer_ok(lin0, obs_dim, n_nodes, deg, hidden, global_cols=False):
+    """The first encoder layer of an agent model fits agent_first_layer: it has a bias and reads the joint
+    observation [env obs | (deg + 1) H readout (| H global mean)] (the widths pack_dqn_first reorders)."""
+    return lin0.bias is not None and lin0.in_features == obs_dim + (deg + 1 + int(bool(global_cols))) * hidden
+
+
+@torch.no_grad()
+def agent_first_layer(lin0, env_obs, obs_dim, state, h_prev, nbr, agent_node, out, ldo=None, hidden=None,
+                      obs_gemm=None, global_cols=False):
+    """out rows (stride ldo) = act(lin0([env obs | NetMon readout])) for the first encoder layer `lin0` of any agent
+    model (DQN, DGN, DQNR, CommNet: encoder.linear_layers[0]) with the readout gathered inside the GEMM's A load
+    (GM_A_READOUT), so the joint observation rows are never written. The arguments are dqn_q's: plain env rows, the
+    GEMM-ready env copy with folded weights (obs_gemm, obs_dim == 6N+10), or global_cols (dense source [env obs |
+    global mean]). The packed weights are cached on lin0 (pack_dqn_first)."""
+    B, A, stride = env_obs.shape
+    N = nbr.shape[1]
+    H = hidden or state.shape[-1] // 2
+    M = B * A
+    fold = obs_gemm is not None and obs_dim == 6 * N + 10 and not global_cols
+    wp, ldw, b, x3 = pack_dqn_first(lin0, obs_dim, N if fold else None, H if global_cols else None)
+    if global_cols:
+        src, ks = dense(env_obs.data_ptr(), stride, obs_dim + H), obs_dim + H
+    elif fold:
+        src, ks = dense(obs_gemm.data_ptr(), obs_gemm.stride(1), obs_dim - 2), obs_dim - 2
+    else:
+        src, ks = dense(env_obs.data_ptr(), stride, obs_dim), obs_dim
+    a0 = readout(state.data_ptr(), state.shape[-1], h_prev.data_ptr(), h_prev.stride(0), nbr, agent_node, N, H)
+    gemm(a0, src, wp.data_ptr(), ldw, b.data_ptr(), M, lin0.out_features,
+         _epi(lin0.act), out.data_ptr(), out.stride(0) if ldo is None else ldo,
+         tag=lin0.tag and f"linear:{lin0.tag}:{M}x{lin0.out_features}x{a0.k + ks}", x3=x3)
+    return out
+
+
+def agent_encoder(mlp, tables, M, scratch, out=None, ldo=None):
+    """An agent model's MLP encoder on a fused NetMonWrapper's tables (tables = (args, kwargs) of agent_first_layer
+    after lin0: policy.EpsilonGreedy.fused_tables): layer 1 on the READOUT source, the others as mlp_rows runs
+    them (same scratch keys); the last layer writes into `out` (stride ldo) when given."""
+    layers = mlp.linear_layers
+    lin0 = layers[0]
+    if len(layers) == 1 and out is not None:
+        h1, ld1 = out, ldo
+    else:
+        h1 = scratch(("mlp", id(mlp), 0), M, lin0.out_features)
+        ld1 = h1.stride(0)
+    args, kw = tables
+    agent_first_layer(lin0, *args, h1, ld1, **kw)
+    if len(layers) == 1:
+        return h1
+    return mlp_rows(mlp, h1, ld1, lin0.out_features, M, scratch, out=out, ldo=ldo, start=1)
+
+
 @torch.no_grad()
 def dqn_q(dqn, env_obs, obs_dim, state, h_prev, nbr, agent_node, scratch, hidden=None, obs_gemm=None,
           global_cols=False):
@@ -595,25 +649,10 @@ def dqn_q(dqn, env_obs, obs_dim, state, h_prev, nbr, agent_node, scratch, hidden
     env_obs with the folded weights (K two columns shorter: whole k tiles at N = 20).
     global_cols: NetMon's output_global_hidden; the H columns after the env observation in env_obs hold the
     graph's mean of h (global_rows), so the dense source is [env obs | global] and obs_gemm is not read."""
-    B, A, stride = env_obs.shape
-    N = nbr.shape[1]
-    H = hidden or state.shape[-1] // 2
-    M = B * A
+    M = env_obs.shape[0] * env_obs.shape[1]
     lin0 = dqn.encoder.linear_layers[0]
-    fold = obs_gemm is not None and obs_dim == 6 * N + 10 and not global_cols
-    wp, ldw, b, x3 = pack_dqn_first(lin0, obs_dim, N if fold else None, H if global_cols else None)
-    if global_cols:
-        src, ks = dense(env_obs.data_ptr(), stride, obs_dim + H), obs_dim + H
-    elif fold:
-        src, ks = dense(obs_gemm.data_ptr(), obs_gemm.stride(1), obs_dim - 2), obs_dim - 2
-    else:
-        src, ks = dense(env_obs.data_ptr(), stride, obs_dim), obs_dim
-    a0 = readout(state.data_ptr(), state.shape[-1], h_prev.data_ptr(), h_prev.stride(0), nbr, agent_node, N, H)
-    h1 = scratch(0, M, lin0.out_features)
-    gemm(a0, src, wp.data_ptr(), ldw, b.data_ptr(), M, lin0.out_features,
-         _epi(lin0.act), h1.data_ptr(), h1.stride(0),
-         tag=lin0.tag and f"linear:{lin0.tag}:{M}x{lin0.out_features}x{a0.k + ks}", x3=x3)
-    h = h1
+    h = agent_first_layer(lin0, env_obs, obs_dim, state, h_prev, nbr, agent_node, scratch(0, M, lin0.out_features),
+                          hidden=hidden, obs_gemm=obs_gemm, global_cols=global_cols)
     hidden = list(dqn.encoder.linear_layers[1:])
     fc = dqn.q_net.fc
     fuse = len(hidden) > 0 and head_ok(hidden[-1], fc)

@@ -353,7 +353,14 @@ def _main(args, rank, world):
             if args.eval_episodes > len(gm.EVAL_SEEDS):
                 print("WARNING: Duplicate eval seeds as number of eval episodes is higher than "
                       f"the number of available seeds ({len(gm.EVAL_SEEDS)})!")
-            base.set_topology_seeds(gm.EVAL_SEEDS, sequential=True, interleave=base.n_env > 1)
+            seeds = gm.EVAL_SEEDS
+            if base.n_nodes != 20:
+                # EVAL_SEEDS are the first 1000 valid 20-router topologies of init seed 476 (src/env/constants.py);
+                # at another size many of them are no valid topology (the reference asserts on a provided seed
+                # that is invalid, src/env/network.py:251): the same definition at this size
+                seeds = gm.build_seed_list(base.n_nodes, 476, min(max(args.eval_episodes, 1), len(gm.EVAL_SEEDS)),
+                                           device=dev.index)
+            base.set_topology_seeds(seeds, sequential=True, interleave=base.n_env > 1)
 
     if args.eval:
         if not lead:  # evaluation runs on rank 0

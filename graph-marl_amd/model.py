@@ -1270,15 +1270,32 @@ class DGN(nn.Module):
         from . import fused as FU
 
         M = x2d.shape[0]
-        hid = self.encoder.out_features
-        nl = len(self.att_layers)
-        qin = scratch(("dgn_qin", id(self)), M, hid * (nl + 1))
+        qin = self._qin(M, scratch)
         FU.mlp_rows(self.encoder, x2d, ldx, k, M, scratch, out=qin, ldo=qin.stride(0))
+        return self._rows_tail(qin, M, scratch, adj, B, A, FU.linear_rows)
+
+    def forward_fused(self, tables, scratch, B, A, adj=None):
+        """forward_rows on a fused NetMonWrapper's tables (policy.EpsilonGreedy.fused_tables): the first encoder
+        layer gathers the NetMon readout in its A load (fused.agent_first_layer), so no joint observation row is
+        read; everything after it is forward_rows'."""
+        from . import fused as FU
+
+        M = B * A
+        qin = self._qin(M, scratch)
+        FU.agent_encoder(self.encoder, tables, M, scratch, out=qin, ldo=qin.stride(0))
+        return self._rows_tail(qin, M, scratch, adj, B, A, FU.linear_rows)
+
+    def _qin(self, M, scratch):
+        return scratch(("dgn_qin", id(self)), M, self.encoder.out_features * (len(self.att_layers) + 1))
+
+    def _rows_tail(self, qin, M, scratch, adj, B, A, head):
+        """Attention layers and Q head on qin, whose first columns hold the encoder's output."""
+        hid = self.encoder.out_features
         for li, layer in enumerate(self.att_layers):
             layer.forward_rows(qin[:, li * hid:], qin.stride(0), adj, B, A, qin[:, (li + 1) * hid:], qin.stride(0),
                                scratch)
         out = scratch(("dgn_q", id(self)), M, self.q_net.fc.out_features)
-        FU.linear_rows(self.q_net.fc, qin, qin.stride(0), M, out, out.stride(0))
+        head(self.q_net.fc, qin, qin.stride(0), M, out, out.stride(0))
         return out
 
 
@@ -1328,15 +1345,18 @@ class DQNR(nn.Module):
         self.state = torch.stack((h1, c1), 1).reshape(B, A, -1)
         return self.q_net(h1.view(B, A, -1))
 
-    def _lstm_rows(self, x, ldx, S_in, S_out, M):
-        """fused LSTM GEMM: S_out = [h' | c'] rows from x rows and S_in = [h | c] rows."""
+    def _lstm_rows(self, x, ldx, S_in, S_out, M, c_in=None, ldc=None):
+        """fused LSTM GEMM: S_out = [h' | c'] rows from x rows and S_in = [h | c] rows (c_in / ldc: the cell
+        rows when they are not S_in's second half)."""
         from . import fused as FU
 
         H = self.lstm.hidden_size
         wp, ldw, bp, x3 = FU.pack_lstm(self.lstm)
+        if c_in is None:
+            c_in, ldc = S_in.data_ptr() + 4 * H, S_in.stride(0)
         FU.gemm(FU.dense(x.data_ptr(), ldx, H), FU.dense(S_in.data_ptr(), S_in.stride(0), H), wp.data_ptr(), ldw,
                 bp.data_ptr(), M, 4 * H, FU.GM_EPI_LSTM, S_out.data_ptr(), S_out.stride(0),
-                S_out.data_ptr() + 4 * H, S_out.stride(0), S_in.data_ptr() + 4 * H, S_in.stride(0),
+                S_out.data_ptr() + 4 * H, S_out.stride(0), c_in, ldc,
                 tag=self.lstm.tag and f"lstm:{self.lstm.tag}:{M}x{4 * H}x{2 * H}", x3=x3)
 
     def _state_rows(self, B, A, M):
@@ -1349,11 +1369,36 @@ class DQNR(nn.Module):
 
         M = x2d.shape[0]
         h = FU.mlp_rows(self.encoder, x2d, ldx, k, M, scratch)
-        S = torch.empty(M, 2 * self.lstm.hidden_size, device=x2d.device)
+        return self._rows_tail(h, M, scratch, adj, B, A, FU.linear_rows)
+
+    def forward_fused(self, tables, scratch, B, A, adj=None, state_out=None):
+        """forward_rows on a fused NetMonWrapper's tables (policy.EpsilonGreedy.fused_tables): the first encoder
+        layer gathers the NetMon readout in its A load (fused.agent_first_layer); everything after it is
+        forward_rows'. state_out [B*A, 2H] (optional, not the storage of
+        `state`) receives the new agent state, so a caller can alternate two fixed buffers (graph replay);
+        `state` becomes its [B, A, 2H] view."""
+        from . import fused as FU
+
+        M = B * A
+        h = FU.agent_encoder(self.encoder, tables, M, scratch)
+        return self._rows_tail(h, M, scratch, adj, B, A, FU.linear_rows, state_out)
+
+    def _new_state(self, M, scratch, state_out):
+        """Allocator of the [M, 2H] state rows of the i-th LSTM step: fresh tensors, or with a caller's state_out
+        two fixed scratch buffers in turn (only the last step writes state_out)."""
+        H2 = 2 * self.lstm.hidden_size
+        if state_out is None:
+            return lambda i: torch.empty(M, H2, device=self.lstm.weight_ih.device)
+        return lambda i: scratch(("agent_S", id(self), i % 2), M, H2)
+
+    def _rows_tail(self, h, M, scratch, adj, B, A, head, state_out=None):
+        """LSTM step from `state` on the encoder's output rows h, then the Q head."""
+        H = self.lstm.hidden_size
+        S = self._new_state(M, scratch, state_out)(0) if state_out is None else state_out.view(M, 2 * H)
         self._lstm_rows(h, h.stride(0), self._state_rows(B, A, M), S, M)
         self.state = S.view(B, A, -1)
         out = scratch(("q", id(self)), M, self.q_net.fc.out_features)
-        FU.linear_rows(self.q_net.fc, S, S.stride(0), M, out, out.stride(0), k=self.lstm.hidden_size)
+        head(self.q_net.fc, S, S.stride(0), M, out, out.stride(0), k=H)
         return out
 
 
@@ -1383,22 +1428,21 @@ class CommNet(DQNR):
         self.state = torch.stack((h, c), 1).reshape(B, A, -1)
         return self.q_net(h.view(B, A, -1))
 
-    def forward_rows(self, x2d, ldx, k, scratch, adj=None, B=None, A=None):
-        from . import fused as FU
-
-        M = x2d.shape[0]
+    def _rows_tail(self, h, M, scratch, adj, B, A, head, state_out=None):
+        """LSTM step from `state`, comm_rounds rounds of gm_agent_comm + the LSTM on [h + comm | h] with the
+        previous step's cell rows, then the Q head."""
         H = self.lstm.hidden_size
-        h = FU.mlp_rows(self.encoder, x2d, ldx, k, M, scratch)
-        S = torch.empty(M, 2 * H, device=x2d.device)
+        new = self._new_state(M, scratch, state_out)
+        last = state_out.view(M, 2 * H) if state_out is not None else None
+        S = last if last is not None and self.comm_rounds == 0 else new(0)
         self._lstm_rows(h, h.stride(0), self._state_rows(B, A, M), S, M)
-        for _ in range(self.comm_rounds):
-            hc = torch.empty(M, 2 * H, device=x2d.device)  # [h + comm | c]
+        for r in range(self.comm_rounds):
+            hc = scratch(("agent_comm", id(self)), M, H)  # h + comm
             L.check(L.lib().gm_agent_comm(L.ptr(S), S.stride(0), L.ptr(adj), B, A, H, L.ptr(hc), hc.stride(0), _s()))
-            hc[:, H:].copy_(S[:, H:])
-            S2 = torch.empty(M, 2 * H, device=x2d.device)
-            self._lstm_rows(hc, hc.stride(0), hc, S2, M)
+            S2 = last if last is not None and r == self.comm_rounds - 1 else new(r + 1)
+            self._lstm_rows(hc, hc.stride(0), hc, S2, M, c_in=S.data_ptr() + 4 * H, ldc=S.stride(0))
             S = S2
         self.state = S.view(B, A, -1)
         out = scratch(("q", id(self)), M, self.q_net.fc.out_features)
-        FU.linear_rows(self.q_net.fc, S, S.stride(0), M, out, out.stride(0), k=H)
+        head(self.q_net.fc, S, S.stride(0), M, out, out.stride(0), k=H)
         return out

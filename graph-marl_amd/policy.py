@@ -10,6 +10,9 @@ import torch
 
 # ε-greedy runs as the env step kernel's prologue (gm_env_policy_step); tests compare it with the two launches
 FUSED_POLICY_STEP = True
+# DGN / DQNR / CommNet take the fused road on a fused NetMonWrapper (forward_fused: no joint observation); False:
+# they read `.obs` like the env-only rollout (tests and tools compare the two roads in one process)
+FUSED_AGENTS = True
 
 
 class EpsilonGreedy:
@@ -29,6 +32,7 @@ class EpsilonGreedy:
         e = self._env
         self.actions = torch.zeros(e.n_env, e.n_data, dtype=torch.int32, device=e.device)
         self._scratch = {}
+        self._state_bufs = None  # recurrent models on the fused road: two fixed state buffers (state_buffer)
 
     def _buf(self, i, m, n):
         key = (i, m, n)
@@ -67,24 +71,75 @@ class EpsilonGreedy:
         self._decay_step()
         return actions
 
-    def _fused_q(self, wenv):
-        """Q rows of the DQN on a fused NetMonWrapper's state tables (fused.dqn_q). With the global readout the
-        dense source is the obs buffer's [env obs | global mean] columns (NetMonWrapper.global_src)."""
-        from . import fused as FU
-
+    def fused_tables(self, wenv):
+        """(args, kwargs) of fused.agent_first_layer / fused.dqn_q after the layer or model: a fused NetMonWrapper's
+        env rows and NetMon state tables. With the global readout the dense source is the obs buffer's [env obs |
+        global mean] columns (NetMonWrapper.global_src)."""
         e = wenv.env
+        H = wenv.netmon.hidden_features
         if getattr(wenv, "global_cols", False):
-            return FU.dqn_q(self._model, wenv.global_src(), e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr,
-                            e.agent_node, self._buf, hidden=wenv.netmon.hidden_features, global_cols=True)
-        return FU.dqn_q(self._model, e.obs_buf, e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr,
-                        e.agent_node, self._buf, hidden=wenv.netmon.hidden_features, obs_gemm=e.obs_gemm)
+            return ((wenv.global_src(), e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr, e.agent_node),
+                    dict(hidden=H, global_cols=True))
+        return ((e.obs_buf, e.obs_dim, wenv.current_netmon_state, wenv.h_prev, e.nbr, e.agent_node),
+                dict(hidden=H, obs_gemm=e.obs_gemm))
 
-    def act(self, wenv):
-        """Fast path for a fused NetMonWrapper: the DQN's first GEMM gathers the NetMon
-        readout from the node state tables instead of reading a materialised joint obs."""
+    def fused_fits(self, wenv):
+        """The model has a fused entry for this wrapper: a DQN, or (FUSED_AGENTS) a DGN / DQNR / CommNet with at
+        most 64 agents (gm_agent_attention / gm_agent_comm) whose first layer reads the wrapper's joint observation
+        (fused.first_layer_ok); DGN and CommNet also need the env's agent adjacency."""
+        from . import fused as FU
+        from .model import DQN, DQNR
+
+        if not getattr(wenv, "fused", False):
+            return False
+        m = self._model
+        if isinstance(m, DQN):
+            return True
+        if not (FUSED_AGENTS and hasattr(m, "forward_fused")):
+            return False
+        e = wenv.env
+        needs_adj = not isinstance(m, DQNR) or hasattr(m, "comm_rounds")
+        return (e.n_data <= 64 and (not needs_adj or getattr(e, "agent_adjacency", False))
+                and FU.first_layer_ok(m.encoder.linear_layers[0], e.obs_dim, e.n_nodes, e.nbr.shape[-1],
+                                      wenv.netmon.hidden_features, getattr(wenv, "global_cols", False)))
+
+    def state_buffer(self, wenv, i=None):
+        """One of this policy's two fixed agent-state buffers [n_env * A, 2H] (recurrent models). The fused forward
+        writes buffer 1 - wenv._cur, so the pair alternates in step with the wrapper's NetMon pair and a captured
+        graph reads and writes the same addresses on every replay; i = None: that output buffer, unless the model's
+        current state lives in it (then the other one)."""
+        e, m = wenv.env, self._model
+        if self._state_bufs is None:
+            self._state_bufs = [torch.zeros(e.n_env * e.n_data, m.get_state_len(), device=e.device) for _ in range(2)]
+        if i is not None:
+            return self._state_bufs[i]
+        i = 1 - getattr(wenv, "_cur", 0)
+        st = m.state
+        if st is not None and st.data_ptr() == self._state_bufs[i].data_ptr():
+            i = 1 - i
+        return self._state_bufs[i]
+
+    def _fused_q(self, wenv):
+        """Q rows of the model on a fused NetMonWrapper's state tables: fused.dqn_q for the DQN, forward_fused for
+        DGN / DQNR / CommNet (adjacency from the env, the recurrent state into this policy's buffer pair). No joint
+        observation row is read or written."""
+        from . import fused as FU
         from .model import DQN
 
-        if not getattr(wenv, "fused", False) or not isinstance(self._model, DQN):
+        args, kw = self.fused_tables(wenv)
+        m = self._model
+        if isinstance(m, DQN):
+            return FU.dqn_q(m, *args, self._buf, **kw)
+        e = wenv.env
+        extra = {"state_out": self.state_buffer(wenv)} if hasattr(m, "state") else {}
+        with torch.no_grad():
+            return m.forward_fused((args, kw), self._buf, e.n_env, e.n_data,
+                                   adj=e.agent_adj if getattr(e, "agent_adjacency", False) else None, **extra)
+
+    def act(self, wenv):
+        """Fast path for a fused NetMonWrapper: the model's first GEMM gathers the NetMon
+        readout from the node state tables instead of reading a materialised joint obs."""
+        if not self.fused_fits(wenv):
             return self(wenv.obs)
         e = wenv.env
         q = self._fused_q(wenv)
@@ -96,9 +151,7 @@ class EpsilonGreedy:
         """act(wenv) then wenv.step_(actions). On the fused NetMon path the ε-greedy draws run
         as the env step kernel's prologue (gm_env_policy_step: one launch instead of two, the
         same draws and actions)."""
-        from .model import DQN
-
-        if not (getattr(wenv, "fused", False) and isinstance(self._model, DQN) and FUSED_POLICY_STEP):
+        if not (FUSED_POLICY_STEP and self.fused_fits(wenv)):
             actions = self.act(wenv)
             if detail is None:
                 wenv.step_(actions)

@@ -3,7 +3,12 @@
 `groups` independent env groups that run on their own HIP streams.
 
 Each group owns a Routing env batch (its own seeds, topology, packets and NetMon state)
-and an ε-greedy policy; the NetMon and DQN modules (and their packed weights) are shared.
+and an ε-greedy policy; the NetMon and agent model modules (and their packed weights) are shared.
+The model is a DQN, DGN, DQNR or CommNet: DGN and CommNet get envs that write the agent adjacency, and
+the recurrent agent state of DQNR / CommNet is kept per group in that group's policy (two fixed buffers
+that alternate in step with the NetMon pair): a group sets `model.state` from its own buffer around its
+forward, zeroes the rows of done agents in place after every env step (src/main.py:710-716) and zeroes
+the whole state at its episode reset (src/main.py:683-686).
 One call to step() enqueues every group's step on that group's stream, so the GPU
 overlaps one group's latency-bound kernels (env step, ε-greedy draws, routing encoder)
 and GEMM tails with another group's GEMMs. Results are identical to running the groups
@@ -24,6 +29,7 @@ import torch
 
 from . import _lib as L
 from . import fused as FU  # noqa: F401  (packed-weight caches shared by the groups)
+from .model import DGN, CommNet
 from .policy import EpsilonGreedy
 from .routing import Routing
 from .wrapper import NetMonWrapper
@@ -78,9 +84,13 @@ class StreamedRollout:
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         extra = (netmon.get_out_features() if netmon is not None else 0) if obs_extra is None else obs_extra
         self.envs, self.wenvs, self.policies, self.streams = [], [], [], []
+        self._model = model
+        self._recurrent = hasattr(model, "state")  # DQNR / CommNet: [h | c] per agent, kept per group
+        self._state = [None] * groups
+        needs_adj = isinstance(model, (DGN, CommNet))
         for g in range(groups):
-            env = Routing(network, n_data, n_env=per, seed=seed + g * per, obs_extra=extra, agent_adjacency=False,
-                          device=dev.index, **env_kw)
+            env = Routing(network, n_data, n_env=per, seed=seed + g * per, obs_extra=extra,
+                          agent_adjacency=needs_adj, device=dev.index, **env_kw)
             wenv = NetMonWrapper(env, netmon, 1) if netmon is not None else _PlainEnv(env)
             pol = EpsilonGreedy(wenv, model, epsilon=epsilon, epsilon_decay=1.0, epsilon_update_freq=100,
                                 step_before_train=0)
@@ -109,8 +119,30 @@ class StreamedRollout:
         for g in range(self.groups):
             self.streams[g].wait_stream(cur)
             with self._on(g):
-                self.wenvs[g].reset_()
+                self._group_reset(g)
         self.ep = 0
+
+    def _group_reset(self, g):
+        """Reset group g's envs (on its stream) and zero its agent state: the buffer the next forward reads."""
+        wenv = self.wenvs[g]
+        wenv.reset_()
+        if self._recurrent:
+            e = self.envs[g]
+            buf = self.policies[g].state_buffer(wenv, getattr(wenv, "_cur", 0))
+            buf.zero_()
+            self._state[g] = buf.view(e.n_env, e.n_data, -1)
+
+    def _group_step(self, g):
+        """One act + env step + NetMon step of group g on the current stream. Recurrent models: the shared model
+        object reads this group's state and the new state's rows of done agents are zeroed in place."""
+        if not self._recurrent:
+            self.policies[g].act_step(self.wenvs[g])
+            return
+        self._model.state = self._state[g]
+        self.policies[g].act_step(self.wenvs[g])
+        st = self._model.state
+        st.mul_((self.envs[g].done == 0).unsqueeze(-1))
+        self._state[g] = st
 
     def _after_caller(self):
         """Order every group stream after what the caller's stream holds (weight copies, edits): one
@@ -124,7 +156,7 @@ class StreamedRollout:
         self._after_caller()
         for g in range(self.groups):
             with self._on(g):
-                self.policies[g].act_step(self.wenvs[g])
+                self._group_step(g)
 
     @torch.no_grad()
     def step(self):
@@ -138,7 +170,7 @@ class StreamedRollout:
         for g in range(self.groups):
             if (self.ep + self._offs[g]) % self.episode_steps == 0:
                 with self._on(g):
-                    self.wenvs[g].reset_()
+                    self._group_reset(g)
         if self.ep >= self.episode_steps:
             self.ep = 0
 
@@ -160,7 +192,7 @@ class StreamedRollout:
                 gr = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gr, stream=self.streams[g]):
                     for _ in range(steps):
-                        self.policies[g].act_step(self.wenvs[g])
+                        self._group_step(g)
                 graphs.append(gr)
             self._graph, self._graphs, self._gsteps = None, graphs, steps
             return
@@ -200,7 +232,7 @@ class StreamedRollout:
                 for g in range(self.groups):
                     if (self.ep + self._offs[g]) % self.episode_steps == 0:
                         with self._on(g):
-                            self.wenvs[g].reset_()
+                            self._group_reset(g)
                 if self.ep >= self.episode_steps:
                     self.ep = 0
                 continue
@@ -216,7 +248,7 @@ class StreamedRollout:
                 for g in due:
                     self.streams[g].wait_stream(cur)
                     with self._on(g):
-                        self.wenvs[g].reset_()
+                        self._group_reset(g)
                 for g in due:
                     cur.wait_stream(self.streams[g])
             if self.ep >= self.episode_steps:
