@@ -21,6 +21,9 @@ INFO_KEYS = ["looped", "throughput", "dropped", "blocked", "n_delays", "sum_dela
 TOPO_FIXED, TOPO_RANDOM, TOPO_LIST, TOPO_SEQUENTIAL = 0, 1, 2, 3
 GM_EVAL_FIELDS = 5
 EVAL_KEYS = ["total_edge_load", "occupied_edges", "packets_on_edges", "total_packet_size", "sum_packet_distances"]
+GM_SERIES_FIELDS = 16
+SERIES_KEYS = ["reward", "throughput", "dropped", "blocked", "looped"] + EVAL_KEYS + [
+    "n_arrived", "sum_delays_arrived", "sum_spr", "spr_min", "feature_diffs_mean", "feature_diffs_max"]
 
 # every symbol the header declares (checked by tests/test_capi.py)
 EXPORTS = [
@@ -38,7 +41,7 @@ EXPORTS = [
     "gm_act_fwd", "gm_act_bwd_z", "gm_obs_from_gemm", "gm_encoder_x3", "gm_step_mse_blocks", "gm_step_mse",
     "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd", "gm_agent_comm_bwd",
     "gm_agent_attention_bwd", "gm_agent_attention_kl", "gm_netmon_global_rows", "gm_netmon_global_bwd",
-    "gm_aux_head_mse", "gm_aux_head_mse_bwd",
+    "gm_aux_head_mse", "gm_aux_head_mse_bwd", "gm_eval_series_step",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
@@ -226,6 +229,8 @@ def lib():
         "gm_aux_head_mse": [vp, i64, i64, i32, vp, i64, vp, i32, vp, i64, vp, i64, vp, i32, vp, vp, vp],
         "gm_aux_head_mse_bwd": [vp, i64, i32, vp, i64, vp, i64, i32, i64, i32, C.c_float, vp, vp, i64, vp, vp, i32, vp,
                                 vp],
+        "gm_eval_series_step": [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i64, i32, i64, vp, vp,
+                                vp, vp, i32, vp],
     }
     for name, at in newer.items():
         if hasattr(L, name) or not os.environ.get("GM_LIB"):

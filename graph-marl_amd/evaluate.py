@@ -1,4 +1,5 @@
-"""Evaluation reducer (reference src/eval.py:33-168 evaluate / get_eval_metrics).
+"""Evaluation reducer (reference src/eval.py:33-168 evaluate / get_eval_metrics) and the data behind the
+reference's evaluation figures (src/eval.py:245-486 create_routing_plots).
 
 Runs `episodes` episodes of `steps_per_episode` steps with the policy in eval mode
 (ε = 0) and reduces the per-step env statistics to the reference's metrics:
@@ -11,16 +12,207 @@ Runs `episodes` episodes of `steps_per_episode` steps with the policy in eval mo
   + eval-only statistics (routing.py:414-441) when the env supports set_eval_info.
 The n_env envs run ceil(episodes / n_env) rounds of parallel episodes; sums are kept in
 fp64 on the device and read back once at the end.
+
+Series (routing envs; `series=True` or an output directory): one gm_eval_series_step launch per step reduces
+every env's step to a row of per-episode tables that stay on the device until the end (`Series`):
+  series        [E, T, len(SERIES_KEYS)]  per-step values, fields in _lib.SERIES_KEYS order
+  feature_diffs [E, T, S]                 per NetMon state column, mean over the nodes of |state_t - state_t-1|
+  done_agents   [E, A]                    agents that ever finished in the episode
+  distance_map  [E, D, 3]                 count / sum / sum of squares of the steps taken by arrived packets,
+                                          keyed by their shortest-path length
+Env b of round r is episode r * n_env + b. "state_t" is the NetMon state the policy acts on at step t (after
+reset's start-up iterations for t = 0); state_-1 = 0 and a run without NetMon has zero drift, as in the reference.
+Files (output_dir): metrics.json, series.npz (the tables, `fields`, `episodes`, `steps`, `detailed`), lzma_d.pk
+(the reference's pickle, `pickle_dict`), and node_state_aux.npz with output_node_state_aux. Plots are not drawn.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
 
+PICKLE_KEYS = ["feature_diffs_mean", "feature_diffs_max", "throughput", "delays_arrived_mean", "looped", "reward",
+               "dropped", "episode_done_agents"]
+# distance-map slots: shortest-path lengths 0 .. DIST_BOUND - 2, the last slot catches anything longer
+DIST_BOUND = 512
+
+
+def _need_device_bytes(n, what, dev):
+    free = torch.cuda.mem_get_info(dev)[0]
+    if n > free:
+        raise ValueError(f"evaluate: {what} needs {n} bytes ({n / 2**30:.2f} GiB) of device memory, {free} are free; "
+                         "use fewer envs, episodes or steps")
+
+
+class Series:
+    """Device tables of the per-step series and their per-step launch (gm_eval_series_step)."""
+
+    def __init__(self, env, episodes, steps, node_state_aux=False, dist_bound=DIST_BOUND):
+        from .wrapper import NetMonWrapper
+
+        self.env = env
+        self.base = base = env.get() if hasattr(env, "get") else env
+        self.E, self.T, self.D = int(episodes), int(steps), int(dist_bound)
+        B, A, N, dev = base.n_env, base.n_data, base.n_nodes, base.device
+        self.B, self.A, self.N, self.dev = B, A, N, dev
+        netmon = getattr(env, "netmon", None)
+        self.has_state = netmon is not None
+        self.S = int(netmon.get_state_size()) if self.has_state else 1
+        # fused wrapper: the states of step t and t - 1 are its two state buffers between the env step and the
+        # NetMon step (NetMonWrapper.step_ before_netmon); anything else keeps one copy of the state per step
+        self.inplace = isinstance(env, NetMonWrapper) and bool(env.fused)
+        E, T, S, D = self.E, self.T, self.S, self.D
+        _need_device_bytes(8 * E * (T * (L.GM_SERIES_FIELDS + S) + 3 * D) + E * A, "the series tables", dev)
+        self.series = torch.zeros(E, T, L.GM_SERIES_FIELDS, dtype=torch.float64, device=dev)
+        self.feature_diffs = torch.zeros(E, T, S, dtype=torch.float64, device=dev)
+        self.done_agents = torch.zeros(E, A, dtype=torch.uint8, device=dev)
+        self.distance_map = torch.zeros(E, D, 3, dtype=torch.float64, device=dev)
+        self.detail = {"done_steps": torch.zeros(B, A, dtype=torch.int32, device=dev),
+                       "done_opt": torch.zeros(B, A, dtype=torch.int32, device=dev),
+                       "success": torch.zeros(B, A, dtype=torch.uint8, device=dev)}
+        self.cur = self.prev = None
+        self.e0 = self.n_active = 0
+        self.aux = bool(node_state_aux)
+        self.node_state = self.node_aux = None
+        if self.aux:
+            self.node_state = np.zeros((E, T, N, S), np.float32)
+            self.node_aux = np.zeros((E, T, N, N), np.float32)
+
+    def begin_round(self, r):
+        self.e0 = r * self.B
+        self.n_active = min(self.B, self.E - self.e0)
+        self.cur = self.prev = None
+        if self.aux:  # one round's states on the device, copied to the host once per round
+            n = 4 * self.B * self.T * self.N * (self.S + self.N)
+            self._st = self._ax = None
+            _need_device_bytes(n, f"one round of node states ([{self.B}, {self.T}, {self.N}, {self.S}] + "
+                                  f"[{self.B}, {self.T}, {self.N}, {self.N}] float32)", self.dev)
+            self._st = torch.zeros(self.B, self.T, self.N, self.S, device=self.dev)
+            self._ax = torch.zeros(self.B, self.T, self.N, self.N, device=self.dev)
+
+    def _state(self):
+        st = getattr(self.env, "current_netmon_state", None) if self.has_state else None
+        return None if st is None else st.reshape(self.B, self.N, self.S)
+
+    def step(self, actions, t):
+        """One env step with the detail buffers filled, and the step's launch -> (reward, done, info) as
+        env.step returns them."""
+        env, base = self.env, self.base
+        if self.aux:
+            st = self._state()
+            if st is not None:
+                self._st[:, t] = st
+            self._ax[:, t] = base.get_node_aux()
+        if self.inplace:
+            env.step_(actions, self.detail, before_netmon=lambda: self._launch(
+                t, env.current_netmon_state, env.last_netmon_state if t > 0 else None))
+        else:
+            st = self._state()
+            self.prev, self.cur = self.cur, (None if st is None else st.float().contiguous().clone())
+            if hasattr(env, "step_"):
+                env.step_(actions, self.detail)
+            else:  # a wrapper that offers only step(): the env picks the buffers up in Routing._detail
+                base.default_detail = self.detail
+                try:
+                    env.step(actions)
+                finally:
+                    base.default_detail = None
+            self._launch(t, self.cur, self.prev if t > 0 else None)
+        info = {k: base.info[:, i] for i, k in enumerate(L.INFO_KEYS)}
+        if base.eval_info_enabled:
+            info.update({k: base.eval_stats[:, i] for i, k in enumerate(L.EVAL_KEYS)})
+        return base.reward, base.done.bool(), info
+
+    def _launch(self, t, cur, prev):
+        base, d = self.base, self.detail
+        if cur is not None:
+            assert cur.is_contiguous() and cur.dtype == torch.float32 and cur.numel() == self.B * self.N * self.S
+            assert prev is None or (prev.is_contiguous() and prev.dtype == torch.float32 and
+                                    prev.numel() == cur.numel())
+        with L.timed("eval_series"):
+            L.check(L.lib().gm_eval_series_step(
+                L.ptr(cur), L.ptr(prev), self.B, self.N, self.S, L.ptr(base.reward), L.ptr(base.done), self.A,
+                L.ptr(base.info), L.ptr(base.eval_stats) if base.eval_info_enabled else None,
+                L.ptr(d["done_steps"]), L.ptr(d["done_opt"]), L.ptr(d["success"]), t, self.T, self.e0, self.n_active,
+                self.E, L.ptr(self.series), L.ptr(self.feature_diffs), L.ptr(self.done_agents),
+                L.ptr(self.distance_map), self.D, L.stream_ptr(self.dev)))
+
+    def end_round(self):
+        if self.aux:
+            e0, n = self.e0, self.n_active
+            self.node_state[e0:e0 + n] = self._st[:n].cpu().numpy()
+            self.node_aux[e0:e0 + n] = self._ax[:n].cpu().numpy()
+            self._st = self._ax = None
+
+    def tables(self):
+        """The host tables (one read-back). The distance map is cut after its longest shortest path: its last
+        slot is the first empty one (still the overflow slot check_distance_map looks at)."""
+        count = self.distance_map[..., 0].sum(0).cpu().numpy()  # packets per key over all episodes
+        check_distance_map(count.reshape(1, -1, 1))
+        keep = int(np.flatnonzero(count).max()) + 2 if count.any() else 2
+        return {"series": self.series.cpu().numpy(), "feature_diffs": self.feature_diffs.cpu().numpy(),
+                "done_agents": self.done_agents.cpu().numpy(),
+                "distance_map": self.distance_map[:, :keep].cpu().numpy()}
+
+
+def check_distance_map(distance_map):
+    """Raise when the overflow slot (the last one) of a distance map [E, D, 3] holds a packet: its shortest
+    path was D - 1 or longer, so the bound must grow; nothing is dropped silently."""
+    if np.any(distance_map[:, -1] != 0):
+        D = distance_map.shape[1]
+        raise ValueError(f"evaluate: a packet's shortest path is >= {D - 1}: the distance map's bound ({D} slots) "
+                         "is too small (evaluate.DIST_BOUND)")
+
+
+def pickle_dict(series, done_agents):
+    """The dict the reference writes to lzma_d.pk (src/eval.py:450-466): seven defaultdict(list) step -> one
+    float per episode, in episode order (delays_arrived_mean only for the episodes with an arrival at that step,
+    src/eval.py:302-305), and episode_done_agents float64 [E, A]. series [E, T, F] in _lib.SERIES_KEYS order."""
+    from collections import defaultdict
+
+    col = {k: i for i, k in enumerate(L.SERIES_KEYS)}
+    d = {k: defaultdict(list) for k in PICKLE_KEYS[:-1]}
+    E, T = series.shape[:2]
+    for e in range(E):
+        for t in range(T):
+            row = series[e, t]
+            for k in ("feature_diffs_mean", "feature_diffs_max", "reward", "dropped", "throughput", "looped"):
+                d[k][t].append(float(row[col[k]]))
+            if row[col["n_arrived"]] > 0:
+                d["delays_arrived_mean"][t].append(float(row[col["sum_delays_arrived"]] / row[col["n_arrived"]]))
+    d["episode_done_agents"] = np.asarray(done_agents, dtype=np.float64)
+    return {k: d[k] for k in PICKLE_KEYS}
+
+
+def write_series(output_dir, tables, detailed=False, node_state=None, node_aux=None):
+    """series.npz and lzma_d.pk (and node_state_aux.npz when the node tables are given) in output_dir."""
+    import lzma
+    import os
+    import pickle
+
+    check_distance_map(tables["distance_map"])
+    os.makedirs(output_dir, exist_ok=True)
+    E, T = tables["series"].shape[:2]
+    np.savez(os.path.join(output_dir, "series.npz"), fields=np.array(L.SERIES_KEYS), episodes=E, steps=T,
+             detailed=bool(detailed), **tables)
+    with lzma.open(os.path.join(output_dir, "lzma_d.pk"), "wb") as f:
+        pickle.dump(pickle_dict(tables["series"], tables["done_agents"]), f)
+    if node_state is not None:
+        np.savez_compressed(os.path.join(output_dir, "node_state_aux"), node_state=node_state, node_aux=node_aux)
+
 
 @torch.no_grad()
-def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True, output_dir=None):
+def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True, output_dir=None, *,
+             output_detailed=False, output_node_state_aux=False, series=None):
+    """-> the metrics dict (and metrics.json in output_dir).
+
+    series / output_dir: collect the per-step series of a routing env (module docstring); output_dir also
+    writes series.npz and lzma_d.pk. A dict passed as `series` receives the host tables.
+    output_node_state_aux: also write node_state_aux.npz (node_state [E, T, N, S], the NetMon state the policy
+    acts on at every step, and node_aux [E, T, N, N] = get_node_aux() before the step); needs output_dir.
+    output_detailed: the reference adds per-episode PNGs; no plots are drawn here and the per-episode
+    throughput already is series[..., throughput], so the flag is only recorded (`detailed` in series.npz)."""
     base = env.get() if hasattr(env, "get") else env
     n_env = base.n_env
     dev = base.device
@@ -30,6 +222,9 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
         env.set_eval_info(True)
     routing = hasattr(base, "info")
     acc = {}
+    ser = None
+    if routing and (series or isinstance(series, dict) or output_dir is not None):
+        ser = Series(env, episodes, steps_per_episode, node_state_aux=output_node_state_aux and output_dir is not None)
 
     def add(key, val):
         acc[key] = acc[key] + val if key in acc else val.clone()
@@ -43,9 +238,14 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
             policy.reset(True)
         if hasattr(policy, "reset_episode"):
             policy.reset_episode()
+        if ser is not None:
+            ser.begin_round(r)
         for step in range(steps_per_episode):
             actions = policy.act(env) if hasattr(policy, "act") else policy(env.obs)
-            _, _, reward, done, info = env.step(actions)
+            if ser is not None:
+                reward, done, info = ser.step(actions, step)
+            else:
+                _, _, reward, done, info = env.step(actions)
             if step + 1 == steps_per_episode:
                 info = env.get_final_info(info)
             add("reward_sum", (reward.to(torch.float64).sum(-1) * w).sum())
@@ -59,6 +259,8 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
             add("steps", w.sum())
             if hasattr(policy, "reset"):  # reset done agents (src/eval.py:111-113)
                 policy.reset(done)
+        if ser is not None:
+            ser.end_round()
     if hasattr(env, "set_eval_info"):
         env.set_eval_info(False)
     h = {k: float(v.item()) for k, v in acc.items()}
@@ -87,6 +289,9 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
                 "packet_sizes_mean": mean(h["total_packet_size"], h["steps"] * A),
                 "packet_distances_mean": mean(h["sum_packet_distances"], h["steps"] * A),
             })
+    tables = ser.tables() if ser is not None else None
+    if isinstance(series, dict) and tables is not None:
+        series.update(tables)
     if output_dir is not None:
         import json
         import os
@@ -94,4 +299,6 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
         os.makedirs(output_dir, exist_ok=True)
         with open(os.path.join(output_dir, "metrics.json"), "w") as f:
             json.dump(metrics, f, indent=4, sort_keys=True)
+        if tables is not None:
+            write_series(output_dir, tables, output_detailed, ser.node_state, ser.node_aux)
     return metrics

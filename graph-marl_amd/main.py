@@ -369,7 +369,8 @@ def _main(args, rank, world):
         switch_to_eval_seeds()
         print("Performing Evaluation")
         metrics = EV.evaluate(env, policy, args.eval_episodes, args.eval_episode_steps, args.disable_progressbar,
-                              args.eval_output_dir)
+                              args.eval_output_dir, output_detailed=args.eval_output_detailed,
+                              output_node_state_aux=args.output_node_state_aux)
         print(json.dumps(metrics, indent=4, sort_keys=True, default=str))
         return metrics
 
@@ -575,7 +576,7 @@ def _main(args, rank, world):
         switch_to_eval_seeds()
         print("Performing Evaluation")
         metrics = EV.evaluate(env, policy, args.eval_episodes, args.eval_episode_steps, args.disable_progressbar,
-                              os.path.join(log_dir, "eval"))
+                              os.path.join(log_dir, "eval"), output_detailed=args.eval_output_detailed)
         print(json.dumps(metrics, indent=4, sort_keys=True, default=str))
     except Exception as e:
         import traceback

@@ -115,6 +115,7 @@ class Routing:
         self.agent_adjacency = agent_adjacency
         self.device = torch.device("cuda", network.device if device is None else device)
         self.eval_info_enabled = False
+        self.default_detail = None  # detail buffers for callers that only reach step() (evaluate's series)
         mode, tseed, lst = network.mode()
         cfg = L.EnvConfig()
         cfg.n_env, cfg.n_nodes, cfg.n_data, cfg.env_var = n_env, network.n_nodes, n_data, int(env_var)
@@ -311,6 +312,8 @@ class Routing:
 
     def _detail(self, detail):
         det = None
+        if detail is None:
+            detail = self.default_detail
         if detail is not None or self.eval_info_enabled:
             det = L.StepDetail()
             if detail is not None:

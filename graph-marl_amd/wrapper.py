@@ -158,8 +158,14 @@ class NetMonWrapper:
         self._netmon_step()
         return self.obs, adj, reward, done, info
 
-    def step_(self, actions, detail=None):
+    def step_(self, actions, detail=None, before_netmon=None):
+        """before_netmon (optional callable): runs between the env step and the NetMon step, while
+        current_netmon_state / last_netmon_state still are the states the policy acted on at this step and at
+        the one before (fused mode: the two buffer pairs; the NetMon step then overwrites the older one).
+        evaluate's series kernel reads the pair there, in place."""
         self.env.step_(actions, detail)
+        if before_netmon is not None:
+            before_netmon()
         self._netmon_step()
 
     def policy_step_(self, q, epsilon, actions, detail=None):

@@ -704,6 +704,44 @@ int gm_agent_attention_bwd(const float* q, const float* k, const float* v, int64
 int gm_agent_attention_kl(const float* q, const float* k, int64_t ld, const float* q_tar, const float* k_tar,
                           int64_t ld_tar, int32_t B, int32_t A, int32_t heads, int32_t dk, float* kl_row, void* stream);
 
+/* ---- Evaluation series (reference src/eval.py:245-486 create_routing_plots) ----
+ * One row of the per-step series per episode and step, float64 [n_episodes, n_steps, GM_SERIES_FIELDS]. */
+enum {
+    GM_SERIES_REWARD = 0,        /* mean of the step's A rewards, summed in fp64 in agent order */
+    GM_SERIES_THROUGHPUT, GM_SERIES_DROPPED, GM_SERIES_BLOCKED, GM_SERIES_LOOPED,       /* info */
+    GM_SERIES_TOTAL_EDGE_LOAD, GM_SERIES_OCCUPIED_EDGES, GM_SERIES_PACKETS_ON_EDGES,    /* the GM_EVAL_* statistics, */
+    GM_SERIES_TOTAL_PACKET_SIZE, GM_SERIES_SUM_PACKET_DISTANCES,                        /* in their order          */
+    GM_SERIES_N_ARRIVED, GM_SERIES_SUM_DELAYS_ARRIVED, GM_SERIES_SUM_SPR,               /* info */
+    GM_SERIES_SPR_MIN,           /* min of done_steps / done_opt over the successful packets, +inf without one */
+    GM_SERIES_FEATURE_DIFFS_MEAN, /* mean over the N * S elements of |state_cur - state_prev| */
+    GM_SERIES_FEATURE_DIFFS_MAX,  /* their maximum */
+    GM_SERIES_FIELDS
+};
+/* One evaluation step of n_env parallel episodes, one launch, one block per env; envs b >= n_active write
+ * nothing. Env b fills row e = e0 + b of the caller's tables (zeroed by the caller before the episode's step 0):
+ *   series        f64 [n_episodes][n_steps][GM_SERIES_FIELDS]: row t, fields above;
+ *   feature_diffs f64 [n_episodes][n_steps][state_size]: row t, per state column the mean over the nodes of
+ *                 |state_cur - state_prev| (np.mean(np.abs(..), axis=0));
+ *   done_agents   u8  [n_episodes][n_agents]: set to 1 where done is set (the OR over the episode's steps);
+ *   distance_map  f64 [n_episodes][dist_bound][3]: count, sum and sum of squares of done_steps of the step's
+ *                 successful packets added to slot done_opt; slot dist_bound - 1 collects every key
+ *                 >= dist_bound - 1 (the overflow slot: a caller sizes dist_bound so that it stays zero).
+ * state_cur / state_prev: f32 [n_env][n_nodes][state_size] contiguous, 16-byte aligned, the NetMon state the
+ * policy acted on at step t and at step t - 1; state_prev NULL = zeros (step 0); both NULL (no NetMon): the
+ * drift fields and the feature_diffs row are 0. reward f32, done u8, done_steps / done_opt i32, success u8:
+ * [n_env][n_agents] (gm_env_step with a gm_step_detail); info f64 [n_env][GM_INFO_FIELDS]; eval f64
+ * [n_env][GM_EVAL_FIELDS] or NULL (zeros).
+ * The difference and abs are fp32; every sum is fp64 in a fixed order (thread, wave butterfly, waves in order)
+ * without atomics: equal inputs give equal bits. n_nodes <= 128, state_size % 4 == 0 and <= 4096, n_agents <= 64,
+ * 0 <= t < n_steps, e0 + n_active <= n_episodes, dist_bound >= 2; anything else: GM_ERR_INVALID_ARG, nothing
+ * launched. Allocates nothing. */
+int gm_eval_series_step(const float* state_cur, const float* state_prev, int32_t n_env, int32_t n_nodes,
+                        int32_t state_size, const float* reward, const uint8_t* done, int32_t n_agents,
+                        const double* info, const double* eval, const int32_t* done_steps, const int32_t* done_opt,
+                        const uint8_t* success, int32_t t, int32_t n_steps, int64_t e0, int32_t n_active,
+                        int64_t n_episodes, double* series, double* feature_diffs, uint8_t* done_agents,
+                        double* distance_map, int32_t dist_bound, void* stream);
+
 /* Build provenance: "src=<16 hex digits of the SHA-256 of the csrc sources and headers> arch=<gfx> hipcc=<version>",
  * fixed when the library is linked (tests/test_capi.py checks it against the tree; bench.py reports it). */
 const char* gm_build_info(void);
