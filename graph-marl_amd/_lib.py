@@ -41,11 +41,11 @@ EXPORTS = [
     "gm_act_fwd", "gm_act_bwd_z", "gm_obs_from_gemm", "gm_encoder_x3", "gm_step_mse_blocks", "gm_step_mse",
     "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd", "gm_agent_comm_bwd",
     "gm_agent_attention_bwd", "gm_agent_attention_kl", "gm_netmon_global_rows", "gm_netmon_global_bwd",
-    "gm_aux_head_mse", "gm_aux_head_mse_bwd", "gm_eval_series_step",
+    "gm_aux_head_mse", "gm_aux_head_mse_bwd", "gm_eval_series_step", "gm_mp_iterate", "gm_mp_iterate_bwd",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
-                  "gm_last_kernel", "gm_last_lnlstm_pw", "gm_gemm_kernel_name"]
+                  "gm_last_kernel", "gm_last_lnlstm_pw", "gm_gemm_kernel_name", "gm_mp_iterate_set_form"]
 
 # Arithmetic form of the fused rollout GEMMs (graph-marl_amd/fused.py): "x3" = split-f16
 # MFMA with fp32 accumulation (default), "f32" = exact fp32 MFMA. GM_GEMM=f32 selects the
@@ -231,6 +231,9 @@ def lib():
                                 vp],
         "gm_eval_series_step": [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i64, i32, i64, vp, vp,
                                 vp, vp, i32, vp],
+        "gm_mp_iterate": [vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp],
+        "gm_mp_iterate_bwd": [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp],
+        "gm_mp_iterate_set_form": [i32],
     }
     for name, at in newer.items():
         if hasattr(L, name) or not os.environ.get("GM_LIB"):

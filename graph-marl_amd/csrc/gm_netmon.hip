@@ -186,6 +186,122 @@ __global__ __launch_bounds__(256) void k_mp_aggregate3(const float* __restrict__
     stv<V>(out + (size_t)row * ldo + (size_t)cv * V, acc);
 }
 
+// K rounds of the aggregate (stateless NetMon, src/model.py:509-554 with rnn_type "none": h = M) with the
+// graphs of a block resident in LDS: two [rows, P] fp32 images (P = row pitch in floats, H or H + 4 so that
+// the 16-byte reads of rows of equal parity do not all start on one bank), read once from HBM, ping-ponged
+// K times, and only h_K (and h_{K-1}, the reference's last_neighbor_h) written back. The pad's effect on the
+// round time has not been measured (at H >= 256 a wave reads one row, so no two rows meet in a lane group).
+// A block holds gpb whole graphs; thread t owns 16-byte lane t % HV of rows t / HV, t / HV + blockDim / HV, .. (blockDim is a
+// multiple of HV: no division inside the rounds). The sorted member lists {n} u nbr(n) are built once per
+// block into LDS as block-local row numbers. Every round does the arithmetic of one k_mp_aggregate launch:
+// forward the members summed in ascending id order, then / count for mean; backward every member scaled by
+// 1 / count(member) for mean, product and sum rounded separately, summed in the same order
+// (bit-identical to the chained launches, tests/test_stateless_gpu.py).
+// BWD: round 0 also adds `add` (the gradient of h_{K-1}), rounded after the sum like a separate add.
+template <bool BWD>
+__global__ __launch_bounds__(1024) void k_mp_iterate(const float* __restrict__ src, long long lds,
+                                                     const float* __restrict__ add, long long lda,
+                                                     const int32_t* __restrict__ nbr, int G, int N, int deg, int H,
+                                                     int P, int gpb, int mode, int iters, float* __restrict__ out,
+                                                     long long ldo, float* __restrict__ prev, long long ldp) {
+    extern __shared__ __attribute__((aligned(16))) float smi[];
+    const int g0 = blockIdx.x * gpb;
+    const int rows = min(gpb, G - g0) * N, cap = gpb * N;
+    float* cur = smi;
+    float* nxt = smi + (size_t)cap * P;
+    int* mlist = reinterpret_cast<int*>(nxt + (size_t)cap * P);  // [cap][deg + 1]
+    int* mcnt = mlist + (size_t)cap * (deg + 1);                 // [cap]
+    float* mscale = reinterpret_cast<float*>(mcnt + cap);        // [cap] (BWD, mean)
+    const int HV = H >> 2, D1 = deg + 1;
+    const int cv4 = ((int)threadIdx.x % HV) * 4, r0 = (int)threadIdx.x / HV, rstep = (int)blockDim.x / HV;
+    const size_t grow0 = (size_t)g0 * N;
+    for (int lr = threadIdx.x; lr < rows; lr += blockDim.x) {
+        const int n = lr % N, base = lr - n;
+        int mem[MAXDEG + 1];
+        const int cnt = members(nbr + (grow0 + lr) * deg, deg, n, mem);
+        for (int q = 0; q < cnt; q++) mlist[lr * D1 + q] = base + mem[q];
+        mcnt[lr] = cnt;
+        if (BWD) mscale[lr] = 1.0f / (float)cnt;
+    }
+    for (int lr = r0; lr < rows; lr += rstep)
+        *reinterpret_cast<float4*>(cur + (size_t)lr * P + cv4) =
+            *reinterpret_cast<const float4*>(src + (grow0 + lr) * lds + cv4);
+    __syncthreads();
+    for (int it = 0; it < iters; it++) {
+        for (int lr = r0; lr < rows; lr += rstep) {
+            const int cnt = mcnt[lr];
+            const int* ml = mlist + lr * D1;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!BWD) {
+                acc = *reinterpret_cast<const float4*>(cur + (size_t)ml[0] * P + cv4);
+                for (int q = 1; q < cnt; q++) acc = f4add(acc, *reinterpret_cast<const float4*>(cur + (size_t)ml[q] * P + cv4));
+                if (mode == 1) {
+                    acc.x = acc.x / cnt;
+                    acc.y = acc.y / cnt;
+                    acc.z = acc.z / cnt;
+                    acc.w = acc.w / cnt;
+                }
+            } else {
+                for (int q = 0; q < cnt; q++) {
+                    const int m = ml[q];
+                    float4 x = *reinterpret_cast<const float4*>(cur + (size_t)m * P + cv4);
+                    if (mode == 1) {
+                        const float s = mscale[m];
+                        x = make_float4(__fmul_rn(x.x, s), __fmul_rn(x.y, s), __fmul_rn(x.z, s), __fmul_rn(x.w, s));
+                    }
+                    acc = q == 0 ? x
+                                 : make_float4(__fadd_rn(acc.x, x.x), __fadd_rn(acc.y, x.y), __fadd_rn(acc.z, x.z),
+                                               __fadd_rn(acc.w, x.w));
+                }
+                if (it == 0 && add) {
+                    const float4 a = *reinterpret_cast<const float4*>(add + (grow0 + lr) * lda + cv4);
+                    acc = make_float4(__fadd_rn(acc.x, a.x), __fadd_rn(acc.y, a.y), __fadd_rn(acc.z, a.z),
+                                      __fadd_rn(acc.w, a.w));
+                }
+            }
+            *reinterpret_cast<float4*>(nxt + (size_t)lr * P + cv4) = acc;
+        }
+        __syncthreads();
+        float* t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    for (int lr = r0; lr < rows; lr += rstep) {
+        *reinterpret_cast<float4*>(out + (grow0 + lr) * ldo + cv4) =
+            *reinterpret_cast<const float4*>(cur + (size_t)lr * P + cv4);
+        if (!BWD)
+            *reinterpret_cast<float4*>(prev + (grow0 + lr) * ldp + cv4) =
+                *reinterpret_cast<const float4*>(nxt + (size_t)lr * P + cv4);
+    }
+}
+
+// the chained form's pieces: out = h0 and prev = 0 (K = 0), and x += y over strided rows (the backward's add)
+template <int V>
+__global__ __launch_bounds__(256) void k_mp_copy_rows(const float* __restrict__ h, long long ldh, long long rows,
+                                                      int HV, float* __restrict__ out, long long ldo,
+                                                      float* __restrict__ prev, long long ldp) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= rows * HV) return;
+    const long long row = gid / HV;
+    const int c = (int)(gid - row * HV) * V;
+    stv<V>(out + row * ldo + c, ldv<V>(h + row * ldh + c));
+    if (prev) stv<V>(prev + row * ldp + c, zerov<V>());
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_mp_add_rows(float* __restrict__ x, long long ldx, const float* __restrict__ y,
+                                                     long long ldy, long long rows, int HV) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= rows * HV) return;
+    const long long row = gid / HV;
+    const int c = (int)(gid - row * HV) * V;
+    Vec<V> a = ldv<V>(x + row * ldx + c);
+    const Vec<V> b = ldv<V>(y + row * ldy + c);
+#pragma unroll
+    for (int i = 0; i < V; i++) a.v[i] = a.v[i] + b.v[i];
+    stv<V>(x + row * ldx + c, a);
+}
+
 // readout: out row r of graph g = [h_final[v], h_prev[nbr(v,0..deg-1)]], v = agent_node or r.
 // Output rows may sit inside a wider joint observation (stride); V-wide stores.
 template <int V>
@@ -606,6 +722,159 @@ extern "C" int gm_mp_aggregate_bwd(const float* dout, const int32_t* nbr, int32_
     if (!dout || !nbr || !dh || G <= 0 || N <= 0 || deg < 0 || deg > MAXDEG || H <= 0 || mode < 0 || mode > 1)
         return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_aggregate_bwd: bad arguments");
     return launch_agg<true>(dout, nbr, G, N, deg, H, mode, dh, stream);
+}
+
+// gm_mp_iterate[_bwd]: K rounds in one LDS-resident launch where the graph fits and the rows are 16-byte lanes,
+// the chained per-round launches otherwise (gm_mp_iterate_set_form: -1 per shape, 0 chain, 1 LDS where eligible)
+static int g_iterate_form = -1;
+extern "C" int gm_mp_iterate_set_form(int32_t form) {
+    if (form < -1 || form > 1) return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate_set_form: form -1, 0 or 1");
+    g_iterate_form = form;
+    return GM_OK;
+}
+
+namespace {
+constexpr int MP_ITER_MAX_NODES = 65536;      // per graph (header: gm_mp_iterate)
+constexpr size_t MP_ITER_LDS_MAX = 160 * 1024;  // LDS of a CU: one block may take all of it
+struct IterPlan { bool lds; int P, gpb, threads; size_t bytes; };
+
+inline bool al16(const void* p, long long ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0; }
+
+// LDS form: rows of 16-byte lanes, at most 1024 lanes per row, both images of one graph within a CU's LDS.
+// Small graphs are packed until a block's first sweep is full (256 threads); a block whose images leave room
+// for no second block on the CU runs 1024 threads instead.
+IterPlan iter_plan(int G, int N, int deg, int H, int iters, bool aligned) {
+    IterPlan p{false, 0, 1, 256, 0};
+    if (!aligned || H % 4 != 0 || H / 4 > 1024 || iters < 1 || g_iterate_form == 0) return p;
+    const int HV = H / 4;
+    p.P = H % 64 == 0 ? H : H + 4;
+    auto bytes = [&](int gpb) {
+        return (size_t)gpb * N * (2 * (size_t)p.P * 4 + (size_t)(deg + 1) * 4 + 8);
+    };
+    if (bytes(1) > MP_ITER_LDS_MAX) return p;
+    int gpb = 1;
+    while (gpb < 16 && (long long)gpb * N * HV < 256 && bytes(gpb + 1) <= 40 * 1024) gpb++;
+    p.gpb = gpb;
+    p.bytes = bytes(gpb);
+    p.threads = p.bytes > 80 * 1024 ? 1024 : 256;
+    if (HV > p.threads) p.threads = 1024;
+    p.threads = p.threads / HV * HV;
+    // K = 1 has nothing to fuse: the chained form is the copy of h0 into prev plus one aggregate launch (4 images
+    // moved against 3). Measured: the LDS form wins 11-12 % in the class of small graphs with several
+    // blocks per CU (N = 20, H = 128) and ties where a block fills most of a CU's LDS (N = 100), which stays chained
+    p.lds = g_iterate_form == 1 || iters >= 2 || p.bytes <= 40 * 1024;
+    return p;
+}
+
+template <bool BWD>
+int launch_iterate(const IterPlan& p, const float* src, long long lds, const float* add, long long lda,
+                   const int32_t* nbr, int G, int N, int deg, int H, int mode, int iters, float* out, long long ldo,
+                   float* prev, long long ldp, void* stream) {
+    // more than 64 KB of dynamic LDS needs the limit raised; set per call (cheap next to such a launch, and right
+    // for every thread and device)
+    if (p.bytes > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)(k_mp_iterate<BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)MP_ITER_LDS_MAX) != hipSuccess)
+        return gm_fail(GM_ERR_HIP, "gm_mp_iterate: raising the LDS limit failed");
+    GM_RAN(BWD ? "k_mp_iterate<bwd>" : "k_mp_iterate<fwd>");
+    hipLaunchKernelGGL(k_mp_iterate<BWD>, dim3((unsigned)((G + p.gpb - 1) / p.gpb)), dim3(p.threads), p.bytes,
+                       (hipStream_t)stream, src, lds, add, lda, nbr, G, N, deg, H, p.P, p.gpb, mode, iters, out, ldo,
+                       prev, ldp);
+    return launched();
+}
+}  // namespace
+
+extern "C" int gm_mp_iterate(const float* h0, int64_t ld0, const int32_t* nbr, int32_t G, int32_t N, int32_t deg,
+                             int32_t H, int32_t mode, int32_t iters, float* out, int64_t ldo, float* prev,
+                             int64_t ldp, void* stream) {
+    if (!h0 || !nbr || !out || G <= 0 || N <= 0 || deg < 0 || deg > MAXDEG || H <= 0 || mode < 0 || mode > 1 ||
+        ld0 < H || ldo < H || (prev && ldp < H))
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate: bad arguments (deg <= 8, ld >= H)");
+    if (iters < 0) return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate: iters < 0");
+    if (iters >= 1 && !prev) return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate: prev is required for iters >= 1");
+    if (N > MP_ITER_MAX_NODES) return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate: n_nodes > 65536");
+    if (out == h0 || prev == h0 || out == prev)
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate: h0, out and prev must be three buffers");
+    const bool aligned = al16(h0, ld0) && al16(out, ldo) && al16(prev, ldp);
+    const IterPlan p = iter_plan(G, N, deg, H, iters, aligned);
+    if (p.lds)
+        return launch_iterate<false>(p, h0, ld0, nullptr, 0, nbr, G, N, deg, H, mode, iters, out, ldo, prev, ldp, stream);
+    if (iters == 0) {
+        int V = std::min(vec_width(H, ld0, h0), vec_width(H, ldo, out));
+        if (prev) V = std::min(V, vec_width(H, ldp, prev));
+        const long long rows = (long long)G * N;
+        GM_VLAUNCH(k_mp_copy_rows, V, dim3(nblocks(rows * (H / V), 256)), h0, (long long)ld0, rows, H / V, out,
+                   (long long)ldo, prev, (long long)ldp);
+        return launched();
+    }
+    // chained launches: h_r lands in out when K - r is even, in prev otherwise (K = 1: prev is a copy of h0)
+    if (iters == 1) {
+        const int V = std::min(vec_width(H, ld0, h0), vec_width(H, ldp, prev));
+        const long long rows = (long long)G * N;
+        GM_VLAUNCH(k_mp_copy_rows, V, dim3(nblocks(rows * (H / V), 256)), h0, (long long)ld0, rows, H / V, prev,
+                   (long long)ldp, (float*)nullptr, 0ll);
+        const int rc = launched();
+        if (rc != GM_OK) return rc;
+    }
+    const float* in = h0;
+    long long ldi = ld0;
+    for (int r = 1; r <= iters; r++) {
+        float* dst = (iters - r) % 2 == 0 ? out : prev;
+        const long long ldd = (iters - r) % 2 == 0 ? ldo : ldp;
+        const int rc = launch_agg<false>(in, nbr, G, N, deg, H, mode, dst, stream, ldi, ldd);
+        if (rc != GM_OK) return rc;
+        in = dst;
+        ldi = ldd;
+    }
+    return GM_OK;
+}
+
+extern "C" int gm_mp_iterate_bwd(const float* d_out, int64_t ldd, const float* d_prev, int64_t ldq,
+                                 const int32_t* nbr, int32_t G, int32_t N, int32_t deg, int32_t H, int32_t mode,
+                                 int32_t iters, float* d_h0, int64_t ld, void* stream) {
+    if (!d_out || !nbr || !d_h0 || G <= 0 || N <= 0 || deg < 0 || deg > MAXDEG || H <= 0 || mode < 0 || mode > 1 ||
+        ldd < H || ld < H || (d_prev && ldq < H))
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate_bwd: bad arguments (deg <= 8, ld >= H)");
+    if (iters < 0) return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate_bwd: iters < 0");
+    if (N > MP_ITER_MAX_NODES) return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate_bwd: n_nodes > 65536");
+    if (d_h0 == d_out || d_h0 == d_prev)
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_mp_iterate_bwd: d_h0 must not alias an input");
+    hipStream_t st = (hipStream_t)stream;
+    const long long rows = (long long)G * N;
+    if (iters == 0) {
+        const int V = std::min(vec_width(H, ldd, d_out), vec_width(H, ld, d_h0));
+        GM_VLAUNCH(k_mp_copy_rows, V, dim3(nblocks(rows * (H / V), 256)), d_out, (long long)ldd, rows, H / V, d_h0,
+                   (long long)ld, (float*)nullptr, 0ll);
+        return launched();
+    }
+    const bool aligned = al16(d_out, ldd) && al16(d_h0, ld) && al16(d_prev, ldq);
+    const IterPlan p = iter_plan(G, N, deg, H, iters, aligned);
+    if (p.lds)
+        return launch_iterate<true>(p, d_out, ldd, d_prev, ldq, nbr, G, N, deg, H, mode, iters, d_h0, ld, nullptr, 0,
+                                    stream);
+    // chained launches: one stream-ordered scratch image for the ping-pong of K >= 2
+    float* tmp = nullptr;
+    if (iters >= 2 && hipMallocAsync((void**)&tmp, (size_t)rows * H * sizeof(float), st) != hipSuccess)
+        return gm_fail(GM_ERR_OOM, "gm_mp_iterate_bwd: scratch allocation failed");
+    // round r = 1..K writes d_h0 when K - r is even, the scratch otherwise
+    const float* in = d_out;
+    long long ldi = ldd;
+    int rc = GM_OK;
+    for (int r = 1; r <= iters && rc == GM_OK; r++) {
+        float* dst = (iters - r) % 2 == 0 ? d_h0 : tmp;
+        const long long ldt = (iters - r) % 2 == 0 ? (long long)ld : (long long)H;
+        rc = launch_agg<true>(in, nbr, G, N, deg, H, mode, dst, stream, ldi, ldt);
+        if (rc == GM_OK && r == 1 && d_prev) {
+            const int V = std::min(vec_width(H, ldt, dst), vec_width(H, ldq, d_prev));
+            GM_VLAUNCH(k_mp_add_rows, V, dim3(nblocks(rows * (H / V), 256)), dst, ldt, d_prev, (long long)ldq, rows,
+                       H / V);
+            rc = launched();
+        }
+        in = dst;
+        ldi = ldt;
+    }
+    if (tmp && hipFreeAsync(tmp, st) != hipSuccess && rc == GM_OK) rc = gm_fail(GM_ERR_HIP, "gm_mp_iterate_bwd: free");
+    return rc;
 }
 
 // readout, one wave per output row (the row's node and neighbour ids read once, as wave-uniform

@@ -502,9 +502,13 @@ def _cell_step(netmon, cell, x_src, h_ptr, ldh, c_ptr, ldc, S, M, tag_kind):
 
 
 def fused_ok(netmon):
-    """The fused no-grad NetMon step covers lstm / lnlstm / gru with state carry-over and the
-    neighbour readout (the reference's NetMonWrapper configuration on routing graphs), with or without the
-    global mean (output_global_hidden: gm_netmon_global_rows, H <= 1024)."""
+    """The fused no-grad NetMon step covers lstm / lnlstm / gru with state carry-over, and the stateless form
+    (rnn_type "none": one gm_mp_iterate after the encoder), with the neighbour readout (the reference's
+    NetMonWrapper configuration on routing graphs), with or without the global mean (output_global_hidden:
+    gm_netmon_global_rows, H <= 1024)."""
+    if netmon.rnn_type == "none":  # stateless: nothing carried, rnn_carryover is irrelevant (gm_mp_iterate)
+        return (netmon.output_neighbor_hidden and netmon.hidden_features % 32 == 0
+                and (not netmon.output_global_hidden or netmon.hidden_features <= 1024))
     return (netmon.rnn_type in ("lstm", "lnlstm", "gru") and netmon.rnn_carryover and netmon.output_neighbor_hidden
             and netmon.hidden_features % 32 == 0
             and (not netmon.output_global_hidden or netmon.hidden_features <= 1024))
@@ -519,13 +523,14 @@ def global_rows(state, ld_state, G, N, H, rows, out, ld_out):
 
 @torch.no_grad()
 def netmon_step(netmon, node_obs, nbr, state, out=None, last_out=None):
-    """One NetMon step for B graphs. node_obs [B, N, F]; nbr int32 [B, N, deg]; state
-    [B, N, S] (S = 2H [h | c] for lstm / lnlstm, H for gru) or None. Returns (new state
-    [B, N, S], h_prev rows [B*N, S] whose first H columns are the last pre-aggregation h).
-    out / last_out ([B*N, S], optional) receive the new state and h_prev, so a caller can keep
-    them in fixed buffers (graph replay)."""
+    """One NetMon step for B graphs. node_obs [B, N, F]; nbr int32 [B, N, deg]; state [B, N, S] (S = 2H [h | c]
+    for lstm / lnlstm, H for gru and for the stateless form, which ignores it) or None. Returns (new state
+    [B, N, S], h_prev rows [B*N, S] whose first H columns are the last pre-aggregation h). out / last_out
+    ([B*N, S], optional) receive the new state and h_prev, so a caller can keep them in fixed buffers (graph
+    replay)."""
     if not fused_ok(netmon):
-        raise NotImplementedError("fused NetMon step: lstm / lnlstm / gru with carry-over (else NetMon.forward_graph)")
+        raise NotImplementedError("fused NetMon step: lstm / lnlstm / gru with carry-over or none (else "
+                                  "NetMon.forward_graph)")
     B, N, Fd = node_obs.shape
     H = netmon.hidden_features
     SW = netmon.state_size
@@ -550,10 +555,20 @@ def netmon_step(netmon, node_obs, nbr, state, out=None, last_out=None):
         layers = layers[1:]
     for lin in layers:
         x = _linear(x, x.stride(0), x.shape[1], lin, torch.empty(M, lin.out_features, device=dev))
+    K = netmon.iterations
+    if netmon.rnn_type == "none":
+        # stateless: K aggregation rounds of the encoded rows in one launch, h_K into the state rows and
+        # h_{K-1} into the h_prev rows (row width H, GRU's layout); nothing is carried, `state` is not read
+        S = out.reshape(M, SW) if out is not None else torch.empty(M, SW, device=dev)
+        last = last_out.reshape(M, SW) if last_out is not None else torch.empty(M, SW, device=dev)
+        with L.timed(f"mp_iterate:{M}x{H}x{K}"):
+            L.check(L.lib().gm_mp_iterate(x.data_ptr(), x.stride(0), nbr.data_ptr(), B, N, nbr.shape[-1], H,
+                                          netmon.agg_mode, K, S.data_ptr(), SW, last.data_ptr(), SW, L.stream_ptr()))
+        netmon.state = S.view(B, N, SW)
+        return netmon.state, last
     if state is None:
         state = torch.zeros(B, N, SW, device=dev)
     st = state.reshape(M, SW)
-    K = netmon.iterations
     cstate = SW > H  # LSTMs carry c in the second half of the row
 
     def buf(i):  # storage of S_i (S_0 = obs cell output, S_K = new state, S_{K-1} = h_prev)

@@ -8,6 +8,7 @@ checkpoints load unchanged. The forward arithmetic runs in libgraphmarl_amd:
                            layers: gm_linear_f32, exact fp32 MFMA)
   * gm_lstm_pointwise      nn.LSTMCell gate math
   * gm_mp_aggregate        SimpleAggregation (sum / mean over I + A)
+  * gm_mp_iterate          K aggregation rounds in one launch (the stateless NetMon, rnn_type "none")
   * gm_netmon_readout      [h, last neighbour h] readout fused with the agent gather
 Backward passes use the matching HIP backward kernels; weight/input gradients of
 the dense layers use library GEMMs (torch.mm -> hipBLASLt).
@@ -543,6 +544,45 @@ def mp_aggregate(h, nbr, mode=SUM):
     return _Aggregate.apply(h.contiguous(), nbr, mode)
 
 
+class _MpIterate(torch.autograd.Function):
+    """K aggregation rounds as one node (gm_mp_iterate / gm_mp_iterate_bwd): (h_K, h_{K-1}) of h0."""
+
+    @staticmethod
+    def forward(ctx, h, nbr, mode, iters):
+        G, N, deg = nbr.shape
+        H = h.shape[-1]
+        out = torch.empty_like(h)
+        prev = torch.empty_like(h)
+        with L.timed(f"mp_iterate:{G * N}x{H}x{iters}"):
+            L.check(L.lib().gm_mp_iterate(L.ptr(h), H, L.ptr(nbr), G, N, deg, H, mode, iters, L.ptr(out), H,
+                                          L.ptr(prev), H, _s()))
+        ctx.save_for_backward(nbr)
+        ctx.mode, ctx.iters = mode, iters
+        ctx.set_materialize_grads(False)  # no readout of h_{K-1}: no add in the backward
+        return out, prev
+
+    @staticmethod
+    def backward(ctx, g, gp):
+        (nbr,) = ctx.saved_tensors
+        G, N, deg = nbr.shape
+        if g is None and (gp is None or ctx.iters == 0):
+            return None, None, None, None
+        g = torch.zeros_like(gp) if g is None else g.contiguous()
+        H = g.shape[-1]
+        gp = None if gp is None or ctx.iters == 0 else gp.contiguous()  # K = 0: prev is the constant 0
+        dh = torch.empty_like(g)
+        with L.timed(f"mp_iterate_bwd:{G * N}x{H}x{ctx.iters}"):
+            L.check(L.lib().gm_mp_iterate_bwd(L.ptr(g), H, L.ptr(gp), H, L.ptr(nbr), G, N, deg, H, ctx.mode,
+                                              ctx.iters, L.ptr(dh), H, _s()))
+        return dh, None, None, None
+
+
+def mp_iterate(h, nbr, mode=SUM, iters=1):
+    """K rounds of SimpleAggregation on rows h [G*N, H] (the stateless NetMon, src/model.py:509-554 with rnn_type
+    "none"): (h_K, h_{K-1}); K = 0 gives (h, 0)."""
+    return _MpIterate.apply(h.contiguous(), nbr, mode, int(iters))
+
+
 class _Readout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hf, hp, nbr, agent_node, out, col0):
@@ -921,7 +961,7 @@ def node_agent_to_index(node_agent):
 
 
 class NetMon(nn.Module):
-    """src/model.py:256-650 for agg_type sum|mean, rnn lstm|lnlstm|gru, carry-over state.
+    """src/model.py:256-650 for agg_type sum|mean, rnn lstm|lnlstm|gru|none, carry-over state.
 
     forward(x, mask, node_agent_matrix, max_degree=None, no_agent_mapping=False) keeps the
     reference signature (dense (I+A) mask / node-agent matrix); forward_graph() is the
@@ -935,7 +975,7 @@ class NetMon(nn.Module):
         if agg_type not in ("sum", "mean"):
             raise NotImplementedError(f"agg_type {agg_type!r}: only sum/mean are built (torch_geometric variants "
                                       "are out of scope)")
-        if not rnn_carryover and iterations < 1:
+        if not rnn_carryover and iterations < 1 and rnn_type != "none":
             raise ValueError("rnn_carryover=False needs netmon iterations >= 1 (the reference's update "
                              "cell output is the stored state)")
         self.encode = MLP(in_features, (*encoder_units, hidden_features), activation=activation)
@@ -960,11 +1000,15 @@ class NetMon(nn.Module):
             self.rnn_obs = GRUCell(hidden_features, hidden_features)
             self.rnn_update = GRUCell(hidden_features, hidden_features)
             self.num_states = 1
+        elif rnn_type == "none":
+            # stateless (src/model.py:394-396, 553-554, 574-576): no cells, h = M in every round; the state is
+            # h_K, kept for the aux head and the node-state outputs only, and rnn_carryover has no effect
+            self.num_states = 1
         else:
             raise NotImplementedError(f"rnn_type {rnn_type!r}")
         # without carry-over the state also keeps the update cell's output (src/model.py:380-391)
         self.cell_states = self.num_states
-        if not rnn_carryover:
+        if not rnn_carryover and rnn_type != "none":
             self.num_states *= 2
         self.hidden_features = hidden_features
         self.state_size = hidden_features * self.num_states
@@ -1039,6 +1083,11 @@ class NetMon(nn.Module):
         B, N, Fdim = x.shape
         H = self.hidden_features
         nc = self.cell_states
+        if self.rnn_type == "none":
+            h = enc if enc is not None else self._encode(x.reshape(B * N, Fdim), nbr, B, N)
+            h, last_nbr = mp_iterate(h, nbr, self.agg_mode, max(self.iterations, 0))
+            self.state = h.reshape(B, N, H)
+            return self._readout(h, last_nbr, nbr, agent_node, out, out_col, B, N)
         if self._hc is not None:
             hs, cs = self._hc[0], self._hc[1]
             st = None
@@ -1071,6 +1120,11 @@ class NetMon(nn.Module):
             # the component-major order: rows hold [h0 of all nodes | h1 of all nodes]
             # (src/model.py:566-567, 447-449)
             self.state = torch.cat((h0.reshape(-1), h.reshape(-1))).reshape(B, N, self.state_size)
+        return self._readout(h, last_nbr, nbr, agent_node, out, out_col, B, N)
+
+    def _readout(self, h, last_nbr, nbr, agent_node, out, out_col, B, N):
+        """src/model.py:457-474: [h | global mean | neighbour h] of every node or of the agents' nodes."""
+        H = self.hidden_features
         if self.output_global_hidden:
             # [h | mean over the graph's nodes of h | neighbour h] (src/model.py:458-469, 624-627)
             hv = h.reshape(B, N, H)

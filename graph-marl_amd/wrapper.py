@@ -7,8 +7,10 @@ GEMMs plus the RNN cells on the HIP kernels (fused.netmon_step: lstm / gru one g
 with the gate math in its epilogue, lnlstm two GEMMs + the LayerNorm-LSTM pointwise kernel); the graph part of the joint
 observation is NOT materialised — the DQN gathers it inside its first GEMM
 (policy.EpsilonGreedy.act). Reading `.obs` (the reference API) materialises the joint
-observation [env obs | readout] on demand. Unfused mode runs NetMon.forward_graph and writes
-the readout into the joint observation buffer after every step.
+observation [env obs | readout] on demand. A stateless NetMon (rnn_type "none") takes the same
+road: its step is the encoder plus one gm_mp_iterate that writes h_K and h_{K-1} into the current
+buffer pair. Unfused mode runs NetMon.forward_graph and writes the readout into the joint
+observation buffer after every step.
 
 Global readout (NetMon output_global_hidden, --netmon-global), fused mode: the joint observation is
 [env obs | h | global | nbr x 3] with global = the mean of h over the graph's nodes. After every NetMon step

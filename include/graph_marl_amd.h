@@ -19,6 +19,7 @@
  *   gm_policy_egreedy                EpsilonGreedy.__call__ (draws + select) src/policy.py:20-64
  *   gm_env_policy_step               EpsilonGreedy.__call__ + Routing.step in one launch (src/main.py:701-703)
  *   gm_mp_aggregate(_bwd)            SimpleAggregation.forward              src/model.py:206-229
+ *   gm_mp_iterate(_bwd)              NetMon._update_node_states, rnn_type "none": K aggregation rounds  src/model.py:509-554
  *   gm_netmon_readout(_bwd)          NetMon._get_neighbor_h + output_to_network_obs src/model.py:582-631
  *   gm_lstm_pointwise(_bwd)          nn.LSTMCell gate math / LayerNorm-free part    src/model.py:379-382, 491, 543
  *   gm_linear_f32                    nn.Linear (+ leaky_relu of MLP)        src/model.py:13-42, 119-125
@@ -216,6 +217,26 @@ int gm_mp_aggregate(const float* h, const int32_t* nbr, int32_t n_graphs, int32_
  * [h | c] state rows in place of the GEMM's AGGREGATE A source. */
 int gm_mp_aggregate_rows(const float* h, int64_t ldh, const int32_t* nbr, int32_t n_graphs, int32_t n_nodes,
                          int32_t deg, int32_t hidden, int32_t mode, float* out, int64_t ldo, void* stream);
+/* K = iters rounds of gm_mp_aggregate_rows (the stateless NetMon, rnn_type "none": h_r = P h_{r-1}, P the
+ * sum / mean over {n} ∪ nbr(n)): out = h_K, prev = h_{K-1} (the reference's last_neighbor_h), both strided
+ * rows like the _rows variant. iters = 0 writes out = h0 and prev = 0 (prev may be NULL then). Every round
+ * gives the fp32 sums of one gm_mp_aggregate_rows launch, so the result is bit-identical to the chained
+ * launches. A graph whose two [n_nodes, hidden] fp32 images fit a CU's LDS, with hidden % 4 == 0 and
+ * 16-byte aligned rows, runs all rounds in one launch with the graph resident in LDS (one read, two
+ * writes); every other shape, and iters = 1 on graphs whose block takes more than 40 KB of LDS, runs the
+ * chained launches inside this call, ping-ponging between out and prev (iters = 1: prev is a copy of h0).
+ * h0, out and prev are three distinct buffers; n_nodes <= 65536; deg <= 8. */
+int gm_mp_iterate(const float* h0, int64_t ld0, const int32_t* nbr, int32_t n_graphs, int32_t n_nodes, int32_t deg,
+                  int32_t hidden, int32_t mode, int32_t iters, float* out, int64_t ldo, float* prev, int64_t ldp,
+                  void* stream);
+/* Its transpose, for symmetric adjacency only (m ∈ nbr(n) <=> n ∈ nbr(m), the precondition of
+ * gm_mp_aggregate_bwd: the rows are gathered through the same table): g = Pᵀ d_out + d_prev,
+ * d_h0 = (Pᵀ)^(iters-1) g; iters = 0: d_h0 = d_out; d_prev may be NULL (no gradient reached h_{K-1}).
+ * Bit-identical to chained gm_mp_aggregate_bwd launches plus the add, LDS-resident under the same
+ * conditions; the chained form of iters >= 2 takes one stream-ordered scratch image (hipMallocAsync). */
+int gm_mp_iterate_bwd(const float* d_out, int64_t ldd, const float* d_prev, int64_t ldq, const int32_t* nbr,
+                      int32_t n_graphs, int32_t n_nodes, int32_t deg, int32_t hidden, int32_t mode, int32_t iters,
+                      float* d_h0, int64_t ld, void* stream);
 /* LayerNorm-LSTM cell after its gate GEMMs (src/layernormlstm.py:24-42, NetMon rnn_type lnlstm):
  * g rows [m][ldg] hold [x W_ih^T | h W_hh^T] (8H floats, gate order i, f, g, o, no bias);
  * gates = LN(gi; ln_in_w, ln_in_b) + LN(gh; ln_hid_w, ln_hid_b) + bias, c1 = LN(sigma(f) c +

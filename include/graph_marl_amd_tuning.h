@@ -30,13 +30,20 @@ int gm_gemm_set_mfma(int32_t shape);
  * -1 (default) = per-shape choice, 0 = register-staged 128 x 128 tile (k_gemm3), 1 = LDS-DMA
  * 128 x 128 tile (4 waves, 2 blocks/CU), 2 = LDS-DMA 128 x 256 tile (8 waves). Process-wide. */
 int gm_gemm_set_dgrad(int32_t form);
+/* Form of gm_mp_iterate / gm_mp_iterate_bwd (same arithmetic, bit for bit; A-B timing, tools/stateless_bench.py):
+ * -1 (default) = per-shape choice (LDS-resident where the graph fits, for iters >= 2 and for iters = 1 on small
+ * graphs), 0 = always
+ * the chained per-round launches, 1 = the LDS-resident launch wherever the shape allows it (iters = 1 too).
+ * Process-wide. */
+int gm_mp_iterate_set_form(int32_t form);
 /* Arithmetic form the GEMM kernels were compiled with, e.g. "x3=lo12 diag=0": x3=lo12 = split-f16
  * with the A operand's low piece scaled by 2^12 in every kernel (the only form since round 5);
  * diag = 0 for the product build, 30 for the k-step stamp build (tools/stamp_bench.py). */
 const char* gm_gemm_form(void);
 /* Diagnostic: the kernel the most recent call on this thread of a dispatching entry point launched ("" before
  * the first such call). NetMon: gm_netmon_readout[_ld], gm_netmon_readout_bwd[_sym], gm_mp_aggregate[_rows|_bwd],
- * gm_lstm_cell_bwd and gm_qhead_bwd report a string literal such as "k_readout_bwd_cs<2>/S=8". GEMMs:
+ * gm_mp_iterate[_bwd] ("k_mp_iterate<fwd|bwd>" or the last chained kernel), gm_lstm_cell_bwd and gm_qhead_bwd
+ * report a string literal such as "k_readout_bwd_cs<2>/S=8". GEMMs:
  * gm_gemm_f32 (gm_linear_f32), gm_gemm_x3, gm_gemm_x3_dgrad, gm_gemm_x3_head, gm_encoder_x3 and
  * gm_gemm_x3_wgrad[2] report the instantiation with its template parameters, e.g.
  * "k_gemm<2,2,2,2,BK16,DENSE,BIAS,occ2>", "k_gemm3<4,1,1,4,BK16,AGGREGATE,LSTM,occ2>" (wave grid WGM x WGN,
