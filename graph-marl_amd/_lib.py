@@ -19,6 +19,7 @@ GM_INFO_FIELDS = 9
 INFO_KEYS = ["looped", "throughput", "dropped", "blocked", "n_delays", "sum_delays", "n_arrived",
              "sum_delays_arrived", "sum_spr"]
 TOPO_FIXED, TOPO_RANDOM, TOPO_LIST, TOPO_SEQUENTIAL = 0, 1, 2, 3
+EDGE_SHUFFLE, EDGE_RANDINT, EDGE_SET = 0, 1, 2
 GM_EVAL_FIELDS = 5
 EVAL_KEYS = ["total_edge_load", "occupied_edges", "packets_on_edges", "total_packet_size", "sum_packet_distances"]
 GM_SERIES_FIELDS = 16
@@ -42,6 +43,7 @@ EXPORTS = [
     "gm_step_mse_bwd", "gm_gru_cell_fwd", "gm_gru_cell_bwd", "gm_lnlstm_cell_bwd", "gm_agent_comm_bwd",
     "gm_agent_attention_bwd", "gm_agent_attention_kl", "gm_netmon_global_rows", "gm_netmon_global_bwd",
     "gm_aux_head_mse", "gm_aux_head_mse_bwd", "gm_eval_series_step", "gm_mp_iterate", "gm_mp_iterate_bwd",
+    "gm_env_randomize_edge_weights",
 ]
 # kernel-form switches (include/graph_marl_amd_tuning.h)
 TUNING_EXPORTS = ["gm_gemm_set_tile", "gm_gemm_set_wgrad", "gm_gemm_set_mfma", "gm_gemm_set_dgrad", "gm_gemm_form",
@@ -191,6 +193,7 @@ def lib():
     L.gm_env_set_topology.argtypes = [vp, i32, i64, vp, i32, i32]
     L.gm_policy_shortest_path.argtypes = [vp, vp, vp]
     L.gm_env_first_hops.argtypes = [vp, vp, vp]
+    L.gm_env_randomize_edge_weights.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.gm_agent_attention.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp]
     L.gm_agent_comm.argtypes = [vp, i64, vp, i32, i32, i32, vp, i64, vp]
     L.gm_gemm_pack_x3_bytes.argtypes = [i32, i32]

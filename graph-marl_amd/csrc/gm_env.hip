@@ -1245,8 +1245,16 @@ struct FirstHopLds {
     int16_t cnt[NC * WAVE];
 };
 
-template <class FS>
-__device__ void first_hops_lds(const EnvDev& d, int env, FS& F) {
+// Rec: what a caller keeps of the search besides the first hops (NoPathRec: nothing, the same code as
+// before the hook existed). relax(src, u, v): v became u's predecessor on the src -> u path; done(src, seen):
+// source src is finished, seen[u * WAVE + lane] is the final src -> u distance.
+struct NoPathRec {
+    __device__ __forceinline__ void relax(int, int, int) {}
+    __device__ __forceinline__ void done(int, const int16_t*) {}
+};
+
+template <class FS, class Rec = NoPathRec>
+__device__ void first_hops_lds(const EnvDev& d, int env, FS& F, Rec&& rec = Rec()) {
     const int l = lane_id();
     const int N = d.N;
     auto& s = F.s;
@@ -1294,9 +1302,11 @@ __device__ void first_hops_lds(const EnvDev& d, int env, FS& F) {
                     seen[u * WAVE + l] = (int16_t)vu;
                     cnt[u * WAVE + l] = (int16_t)c++;
                     first[src * N + u] = v == src ? (uint8_t)u : first[src * N + v];
+                    rec.relax(src, u, v);
                 }
             }
         }
+        rec.done(src, seen);
     }
     __syncthreads();
 }
@@ -1333,6 +1343,121 @@ __global__ __launch_bounds__(64) void k_env_first_hops(EnvDev d, int32_t* out) {
     first_hops_lds(d, env, F);
     const int N = d.N;
     for (int i = lane_id(); i < N * N; i += WAVE) out[(size_t)env * N * N + i] = F.first[i];
+}
+
+// ---------------------------------------------------------------------------
+// Edge-weight change during an episode (network.py:292-351 randomize_edge_weights).
+// One wave per env: (1) the search on the old lengths, keeping first hops and predecessors; (2) the new
+// lengths, drawn from the env's own stream in the reference's order; (3) the search on the new lengths, whose
+// final distances replace the env's apsp rows (the path weight of a shortest path is its distance: the old
+// apsp row is the old weight table and is compared just before it is overwritten); (4) the three proportions.
+// Packets, loads and visited sets are not touched: a packet on an edge keeps its time.
+// LDS: the first-hop image + three N x N byte tables + E lengths (NC = 64: 41 KB, NC = 128: 108 KB).
+// ---------------------------------------------------------------------------
+template <int NC>
+struct ReweighLds {
+    FirstHopLds<NC> F;
+    uint8_t pred[NC * NC];  // predecessor of t on the s -> t path: networkx's path is this chain
+    uint8_t old_first[NC * NC], old_pred[NC * NC];
+    int32_t wlen[NC * 3 / 2];
+};
+
+// the search's predecessors; with apsp also the distances (and how many of them differ from the old ones)
+struct PathRec {
+    uint8_t* pred;
+    int16_t* apsp;  // the env's [N][N] rows (NULL: distances not kept)
+    int N, l;
+    int changed = 0;
+    __device__ __forceinline__ void relax(int src, int u, int v) { pred[src * N + u] = (uint8_t)v; }
+    __device__ __forceinline__ void done(int src, const int16_t* seen) {
+        pred[src * N + src] = (uint8_t)src;
+        if (!apsp) return;
+        for (int u = 0; u < N; u++) {
+            const int16_t nd = seen[u * WAVE + l];
+            changed += apsp[src * N + u] != nd;
+            apsp[src * N + u] = nd;
+        }
+    }
+};
+
+template <int NC>
+__global__ __launch_bounds__(64) void k_env_reweigh(EnvDev d, int mode, int low, int high, int set_a, int set_b,
+                                                    int set_len, const uint8_t* mask, double* stats) {
+    const int env = blockIdx.x;
+    const int l = lane_id();
+    const int N = d.N, E = d.E;
+    if (mask && !mask[env]) {
+        if (l < 3) stats[(size_t)env * 3 + l] = 0.0;
+        return;
+    }
+    __shared__ ReweighLds<NC> S;
+    auto& s = S.F.s;
+    // the old pass writes its distances too: the "old weights" are those of the lengths the old first hops and
+    // predecessors come from, even where apsp was stale (gm_env_set_state with new edge_len and no apsp)
+    PathRec old_rec{S.pred, d.apsp + (size_t)env * N * N, N, l};
+    first_hops_lds(d, env, S.F, old_rec);
+    for (int i = l; i < N * N; i += WAVE) {
+        S.old_first[i] = S.F.first[i];
+        S.old_pred[i] = S.pred[i];
+    }
+    for (int e = l; e < E; e += WAVE) S.wlen[e] = s.elen[e];
+    __syncthreads();
+    if (mode == GM_EDGE_SET) {  // the edge with these sorted endpoints, if the env has it
+        for (int e = l; e < E; e += WAVE)
+            if (s.ea[e] == set_a && s.eb[e] == set_b) S.wlen[e] = set_len;
+    } else {
+        MainRng r = open_rng(d, env, s);
+        if (mode == GM_EDGE_SHUFFLE) {
+            // np.random.shuffle (legacy): i from the top index down, partner j = masked-rejection draw in [0, i]
+            for (int i = E - 1; i >= 1; i--) {
+                const int j = (int)r.randint(i + 1);
+                if (l == 0) {
+                    const int32_t t = S.wlen[i];
+                    S.wlen[i] = S.wlen[j];
+                    S.wlen[j] = t;
+                }
+            }
+        } else {  // np.random.randint(low, high) per edge in edge order
+            for (int e = 0; e < E; e++) {
+                const int v = low + (int)r.randint(high - low);
+                if (l == 0) S.wlen[e] = v;
+            }
+        }
+        close_rng(d, env, r);
+    }
+    __syncthreads();
+    for (int e = l; e < E; e += WAVE) d.edge_len[(size_t)env * E + e] = S.wlen[e];
+    __syncthreads();  // the search reloads the topology image from HBM
+    PathRec rec{S.pred, d.apsp + (size_t)env * N * N, N, l};
+    first_hops_lds(d, env, S.F, rec);
+    // first hop / whole path / weight changed, over the N (N - 1) ordered pairs (lane = source)
+    int n_first = 0, n_path = 0;
+    for (int src = l; src < N; src += WAVE) {
+        for (int t = 0; t < N; t++) {
+            if (t == src) continue;
+            n_first += S.F.first[src * N + t] != S.old_first[src * N + t];
+            int u = t;
+            bool diff = false;
+            for (int g = 0; g < N && u != src; g++) {
+                const int pn = S.pred[src * N + u];
+                if (pn != S.old_pred[src * N + u]) {
+                    diff = true;
+                    break;
+                }
+                u = pn;
+            }
+            n_path += diff;
+        }
+    }
+    n_first = wave_sum_i32(n_first);
+    n_path = wave_sum_i32(n_path);
+    const int n_weight = wave_sum_i32(rec.changed);
+    if (l == 0) {
+        const double pairs = (double)(N * (N - 1));
+        stats[(size_t)env * 3 + 0] = (double)n_first / pairs;
+        stats[(size_t)env * 3 + 1] = (double)n_path / pairs;
+        stats[(size_t)env * 3 + 2] = (double)n_weight / pairs;
+    }
 }
 
 __global__ void k_rng_seed(EnvDev d, const uint32_t* seeds) {
@@ -1656,6 +1781,27 @@ extern "C" int gm_env_first_hops(gm_env* env, int32_t* out, void* stream) {
     if (!env || !out) return gm_fail(GM_ERR_INVALID_ARG, "gm_env_first_hops: null argument");
     if (ncap(env->d.N) == 64) hipLaunchKernelGGL(k_env_first_hops<64>, dim3(env->d.n_env), dim3(64), 0, (hipStream_t)stream, env->d, out);
     else hipLaunchKernelGGL(k_env_first_hops<128>, dim3(env->d.n_env), dim3(64), 0, (hipStream_t)stream, env->d, out);
+    return check_launch();
+}
+
+extern "C" int gm_env_randomize_edge_weights(gm_env* env, int32_t mode, int32_t low, int32_t high, int32_t edge_start,
+                                             int32_t edge_end, int32_t length, const uint8_t* env_mask, double* stats,
+                                             void* stream) {
+    if (!env || !stats) return gm_fail(GM_ERR_INVALID_ARG, "gm_env_randomize_edge_weights: null argument");
+    // lengths live in one byte of the kernels' topology image and in int16 path sums (N * 255 < 2^15)
+    if (mode == GM_EDGE_RANDINT) {
+        if (low < 1 || high <= low || high > 256)
+            return gm_fail(GM_ERR_INVALID_ARG, "gm_env_randomize_edge_weights: randint needs 1 <= low < high <= 256");
+    } else if (mode == GM_EDGE_SET) {
+        // an endpoint outside the graph is an edge no env has: nothing is set (the reference matches no edge)
+        if (edge_start < 0 || edge_end <= edge_start || length < 1 || length > 255)
+            return gm_fail(GM_ERR_INVALID_ARG,
+                           "gm_env_randomize_edge_weights: set needs 0 <= edge_start < edge_end and 1 <= length <= 255");
+    } else if (mode != GM_EDGE_SHUFFLE) {
+        return gm_fail(GM_ERR_INVALID_ARG, "gm_env_randomize_edge_weights: unknown mode");
+    }
+    if (ncap(env->d.N) == 64) hipLaunchKernelGGL(k_env_reweigh<64>, dim3(env->d.n_env), dim3(64), 0, (hipStream_t)stream, env->d, (int)mode, (int)low, (int)high, (int)edge_start, (int)edge_end, (int)length, env_mask, stats);
+    else hipLaunchKernelGGL(k_env_reweigh<128>, dim3(env->d.n_env), dim3(64), 0, (hipStream_t)stream, env->d, (int)mode, (int)low, (int)high, (int)edge_start, (int)edge_end, (int)length, env_mask, stats);
     return check_launch();
 }
 

@@ -38,6 +38,65 @@ PICKLE_KEYS = ["feature_diffs_mean", "feature_diffs_max", "throughput", "delays_
 DIST_BOUND = 512
 
 
+def parse_step(text):
+    """A step index of an evaluation event (--eval-netmon-freeze STEP): a non-negative integer."""
+    try:
+        step = int(text)
+    except ValueError:
+        raise ValueError(f"not a step number: {text!r}") from None
+    if step < 0:
+        raise ValueError(f"step must be >= 0, not {step}")
+    return step
+
+
+def parse_edge_change(text):
+    """STEP:MODE[:ARGS] (--eval-edge-change) -> (step, mode, kwargs of Routing.randomize_edge_weights):
+    50:shuffle, 50:randint:LOW:HIGH, 50:set:A:B:LENGTH, 50:bottleneck-971182936. ValueError on anything else."""
+    from .routing import edge_change_args
+
+    parts = str(text).split(":")
+    if len(parts) < 2:
+        raise ValueError(f"expected STEP:MODE[:ARGS], not {text!r}")
+    step, mode = parse_step(parts[0]), parts[1]
+    want = {"shuffle": 0, "randint": 2, "set": 3, "bottleneck-971182936": 0}
+    if mode not in want:
+        raise ValueError(f"unknown edge-change mode {mode!r} in {text!r}")
+    if len(parts) - 2 != want[mode]:
+        raise ValueError(f"mode {mode} takes {want[mode]} arguments, not {len(parts) - 2}: {text!r}")
+    try:
+        nums = [int(x) for x in parts[2:]]
+    except ValueError:
+        raise ValueError(f"edge-change arguments must be integers: {text!r}") from None
+    kwargs = {}
+    if mode == "randint":
+        kwargs = {"low": nums[0], "high": nums[1]}
+    elif mode == "set":
+        kwargs = {"edge": (nums[0], nums[1]), "length": nums[2]}
+    edge_change_args(mode, **kwargs)  # range checks
+    return step, mode, kwargs
+
+
+class EdgeChange:
+    """Evaluation event: Routing.randomize_edge_weights(mode, **kwargs) in every env; keeps every call's
+    proportions (one call per round of parallel episodes) for metrics["edge_change"]."""
+
+    def __init__(self, step, mode, **kwargs):
+        self.step, self.mode, self.kwargs = int(step), mode, kwargs
+        self.stats = []
+
+    def __call__(self, env):
+        base = env.get() if hasattr(env, "get") else env
+        self.stats.append(base.randomize_edge_weights(self.mode, **self.kwargs))
+
+    def summary(self, episodes):
+        """Env b of call r is episode r * n_env + b: the mean over the first `episodes` rows."""
+        p = np.concatenate(self.stats)[:episodes].mean(0) if self.stats else np.full(3, np.nan)
+        return {"step": self.step, "mode": self.mode, "args": {k: list(v) if isinstance(v, tuple) else v
+                                                               for k, v in self.kwargs.items()},
+                "first_hops_changed": float(p[0]), "paths_changed": float(p[1]),
+                "path_weights_changed": float(p[2])}
+
+
 def _need_device_bytes(n, what, dev):
     free = torch.cuda.mem_get_info(dev)[0]
     if n > free:
@@ -105,8 +164,10 @@ class Series:
                 self._st[:, t] = st
             self._ax[:, t] = base.get_node_aux()
         if self.inplace:
+            # frozen for a step or more: the policy acts on the same state as at the step before (no drift)
             env.step_(actions, self.detail, before_netmon=lambda: self._launch(
-                t, env.current_netmon_state, env.last_netmon_state if t > 0 else None))
+                t, env.current_netmon_state, None if t == 0 else
+                env.current_netmon_state if env.frozen_steps > 0 else env.last_netmon_state))
         else:
             st = self._state()
             self.prev, self.cur = self.cur, (None if st is None else st.float().contiguous().clone())
@@ -202,10 +263,23 @@ def write_series(output_dir, tables, detailed=False, node_state=None, node_aux=N
         np.savez_compressed(os.path.join(output_dir, "node_state_aux"), node_state=node_state, node_aux=node_aux)
 
 
-@torch.no_grad()
 def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True, output_dir=None, *,
              output_detailed=False, output_node_state_aux=False, series=None):
+    """-> the metrics dict (and metrics.json in output_dir): `evaluate_events` without events, the reference's
+    evaluate as it stands (its manual experiments commented out)."""
+    return evaluate_events(env, policy, episodes, steps_per_episode, None, disable_progressbar, output_dir,
+                           output_detailed=output_detailed, output_node_state_aux=output_node_state_aux, series=series)
+
+
+@torch.no_grad()
+def evaluate_events(env, policy, episodes, steps_per_episode, events=None, disable_progressbar=True, output_dir=None,
+                    *, output_detailed=False, output_node_state_aux=False, series=None):
     """-> the metrics dict (and metrics.json in output_dir).
+
+    events: list of (step, callable(env)), or None; each callable runs before the policy acts at that step of every
+    round of parallel episodes (the reference's manual experiments, src/eval.py:92-103: `EdgeChange`, or
+    `lambda env: env.freeze()`). An `EdgeChange` adds metrics["edge_change"]. `evaluate` keeps the reference's
+    parameter list, so the events have this entry point of their own.
 
     series / output_dir: collect the per-step series of a routing env (module docstring); output_dir also
     writes series.npz and lzma_d.pk. A dict passed as `series` receives the host tables.
@@ -241,6 +315,9 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
         if ser is not None:
             ser.begin_round(r)
         for step in range(steps_per_episode):
+            for at, fn in events or ():
+                if at == step:
+                    fn(env)
             actions = policy.act(env) if hasattr(policy, "act") else policy(env.obs)
             if ser is not None:
                 reward, done, info = ser.step(actions, step)
@@ -289,6 +366,9 @@ def evaluate(env, policy, episodes, steps_per_episode, disable_progressbar=True,
                 "packet_sizes_mean": mean(h["total_packet_size"], h["steps"] * A),
                 "packet_distances_mean": mean(h["sum_packet_distances"], h["steps"] * A),
             })
+    for _, fn in events or ():
+        if isinstance(fn, EdgeChange):
+            metrics["edge_change"] = fn.summary(episodes)
     tables = ser.tables() if ser is not None else None
     if isinstance(series, dict) and tables is not None:
         series.update(tables)

@@ -162,7 +162,27 @@ def build_parser():
     # graph-marl_amd
     a("--n-env", type=int, default=1, help="Parallel environment instances per step (graph-marl_amd)")
     a("--log-dir", type=str, default=None, help="Checkpoint / metrics directory (default runs/<date>_<host><comment>)")
+    a("--eval-edge-change", type=EV.parse_edge_change, default=None, metavar="STEP:MODE[:ARGS]",
+      help="Evaluation: change the edge weights before the policy acts at STEP of every episode: "
+           "50:shuffle, 50:randint:LOW:HIGH, 50:set:A:B:LENGTH or 50:bottleneck-971182936. The reference's "
+           "`if step == S` line acts after step S: STEP = S + 1 (graph-marl_amd)")
+    a("--eval-netmon-freeze", type=EV.parse_step, default=None, metavar="STEP",
+      help="Evaluation: freeze NetMon (no message passing) from STEP of every episode on; the reference's "
+           "`if step == S: env.freeze()` is STEP = S + 1 (graph-marl_amd)")
     return p
+
+
+def eval_events(args, env):
+    """The evaluation events of --eval-edge-change / --eval-netmon-freeze (None when neither is given)."""
+    events = []
+    if args.eval_edge_change is not None:
+        step, mode, kwargs = args.eval_edge_change
+        events.append((step, EV.EdgeChange(step, mode, **kwargs)))
+    if args.eval_netmon_freeze is not None:
+        if not hasattr(env, "freeze"):
+            raise SystemExit("--eval-netmon-freeze needs --netmon")
+        events.append((args.eval_netmon_freeze, lambda e: e.freeze()))
+    return events or None
 
 
 MODEL_ARG_KEYS = ["model", "hidden_dim", "netmon", "netmon_dim", "netmon_encoder_dim", "netmon_iterations",
@@ -371,9 +391,10 @@ def _main(args, rank, world):
         print(f"Policy: {type(policy).__name__}")
         switch_to_eval_seeds()
         print("Performing Evaluation")
-        metrics = EV.evaluate(env, policy, args.eval_episodes, args.eval_episode_steps, args.disable_progressbar,
-                              args.eval_output_dir, output_detailed=args.eval_output_detailed,
-                              output_node_state_aux=args.output_node_state_aux)
+        metrics = EV.evaluate_events(env, policy, args.eval_episodes, args.eval_episode_steps, eval_events(args, env),
+                                     args.disable_progressbar, args.eval_output_dir,
+                                     output_detailed=args.eval_output_detailed,
+                                     output_node_state_aux=args.output_node_state_aux)
         print(json.dumps(metrics, indent=4, sort_keys=True, default=str))
         return metrics
 
@@ -588,8 +609,9 @@ def _main(args, rank, world):
             netmon.state = None
         switch_to_eval_seeds()
         print("Performing Evaluation")
-        metrics = EV.evaluate(env, policy, args.eval_episodes, args.eval_episode_steps, args.disable_progressbar,
-                              os.path.join(log_dir, "eval"), output_detailed=args.eval_output_detailed)
+        metrics = EV.evaluate_events(env, policy, args.eval_episodes, args.eval_episode_steps, eval_events(args, env),
+                                     args.disable_progressbar, os.path.join(log_dir, "eval"),
+                                     output_detailed=args.eval_output_detailed)
         print(json.dumps(metrics, indent=4, sort_keys=True, default=str))
     except Exception as e:
         import traceback

@@ -1076,9 +1076,10 @@ class NetMon(nn.Module):
         B, N, Fdim = x.shape
         return self._encode(x.reshape(B * N, Fdim), nbr, B, N)
 
-    def forward_graph(self, x, nbr, agent_node=None, out=None, out_col=0, enc=None):
+    def forward_graph(self, x, nbr, agent_node=None, out=None, out_col=0, enc=None, tables=None):
         """x [B, N, F] node observations, nbr int32 [B, N, deg], agent_node int32 [B, A] or None;
         enc: encode_nodes(x, nbr) computed once by the caller (the same values the encoder gives).
+        tables: a list that receives the readout's source tables [h, neighbour h] (readout_tables).
         Returns [B, A or N, 4H] (or writes into `out` [B, A, W] at column out_col)."""
         B, N, Fdim = x.shape
         H = self.hidden_features
@@ -1087,6 +1088,8 @@ class NetMon(nn.Module):
             h = enc if enc is not None else self._encode(x.reshape(B * N, Fdim), nbr, B, N)
             h, last_nbr = mp_iterate(h, nbr, self.agg_mode, max(self.iterations, 0))
             self.state = h.reshape(B, N, H)
+            if tables is not None:
+                tables[:] = [h, last_nbr]
             return self._readout(h, last_nbr, nbr, agent_node, out, out_col, B, N)
         if self._hc is not None:
             hs, cs = self._hc[0], self._hc[1]
@@ -1120,6 +1123,8 @@ class NetMon(nn.Module):
             # the component-major order: rows hold [h0 of all nodes | h1 of all nodes]
             # (src/model.py:566-567, 447-449)
             self.state = torch.cat((h0.reshape(-1), h.reshape(-1))).reshape(B, N, self.state_size)
+        if tables is not None:
+            tables[:] = [h, last_nbr]
         return self._readout(h, last_nbr, nbr, agent_node, out, out_col, B, N)
 
     def _readout(self, h, last_nbr, nbr, agent_node, out, out_col, B, N):
@@ -1148,6 +1153,14 @@ class NetMon(nn.Module):
             return out
         R = N if agent_node is None else agent_node.shape[1]
         return res.reshape(B, R, -1)
+
+    def readout_tables(self, tables, nbr, agent_node=None, out=None, out_col=0):
+        """The readout of an earlier forward_graph again, from the h / neighbour-h tables it handed out (its
+        `tables` argument), for the agents' current nodes (NetMonWrapper.freeze: src/env/wrapper.py:67-75 maps the
+        kept netmon_out)."""
+        h, last_nbr = tables
+        B, N = nbr.shape[:2]
+        return self._readout(h, last_nbr, nbr, agent_node, out, out_col, B, N)
 
     def forward(self, x, mask, node_agent_matrix=None, max_degree=None, no_agent_mapping=False):
         # the neighbour table holds every neighbour (aggregation always uses the full mask,

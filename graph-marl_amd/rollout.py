@@ -212,7 +212,8 @@ class StreamedRollout:
     @torch.no_grad()
     def run(self, n):
         """n vector steps (graph replays of capture()'s length when captured, else eager)."""
-        if self._graph is None and self._graphs is None:
+        # a captured graph holds the NetMon launches: while a wrapper is frozen the steps run eagerly
+        if (self._graph is None and self._graphs is None) or any(getattr(w, "frozen", False) for w in self.wenvs):
             for _ in range(n):
                 self.step()
             return

@@ -8,6 +8,7 @@ Per-env behaviour is bit-identical to the reference given the same numpy seed.
 """
 import ctypes as C
 import os
+import weakref
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -72,6 +73,16 @@ class Network:
             return L.TOPO_SEQUENTIAL, self.topology_init_seed, self.seeds
         return L.TOPO_LIST, self.topology_init_seed, self.seeds
 
+    def randomize_edge_weights(self, mode, **kwargs):
+        """Network.randomize_edge_weights (src/env/network.py:292-351) on the `Routing` that owns this network
+        (Routing.randomize_edge_weights; env_mask= selects envs). One env: the reference's 3-tuple of floats."""
+        ref = getattr(self, "_routing", None)
+        env = ref() if ref is not None else None
+        if env is None:
+            raise RuntimeError("randomize_edge_weights: this Network belongs to no live Routing env")
+        out = env.randomize_edge_weights(mode, **kwargs)
+        return tuple(float(x) for x in out[0]) if env.n_env == 1 else out
+
 
 def build_seed_list(n_nodes, init_seed, count, excluded=None, device=0):
     """Network.build_seed_list (src/env/network.py:100-120), computed on the GPU."""
@@ -81,6 +92,27 @@ def build_seed_list(n_nodes, init_seed, count, excluded=None, device=0):
     L.check(L.lib().gm_build_seed_list(n_nodes, init_seed, count, None if ex is None else ex.ctypes.data,
                                        0 if ex is None else len(ex), device, out.ctypes.data))
     return [int(s) for s in out]
+
+
+def edge_change_args(mode, **kwargs):
+    """(mode id, low, high, edge_start, edge_end, length) of gm_env_randomize_edge_weights for the reference's
+    mode strings (src/env/network.py:301-321) and "set" (edge=(a, b), length=); ValueError on anything else."""
+    if mode == "shuffle":
+        return L.EDGE_SHUFFLE, 0, 0, 0, 0, 0
+    if mode == "randint":
+        low, high = int(kwargs["low"]), int(kwargs["high"])
+        if not 1 <= low < high <= 256:
+            raise ValueError(f"randint edge weights need 1 <= low < high <= 256, not ({low}, {high})")
+        return L.EDGE_RANDINT, low, high, 0, 0, 0
+    if mode == "bottleneck-971182936":  # the paper's bottleneck link (network.py:309-319)
+        return L.EDGE_SET, 0, 0, 2, 7, 10
+    if mode == "set":
+        a, b = sorted(int(x) for x in kwargs["edge"])
+        length = int(kwargs["length"])
+        if a < 0 or a == b or not 1 <= length <= 255:
+            raise ValueError(f"set edge weight needs two different nodes and 1 <= length <= 255, not {kwargs}")
+        return L.EDGE_SET, 0, 0, a, b, length
+    raise ValueError(f"Unknown mode {mode}")
 
 
 class Routing:
@@ -104,6 +136,7 @@ class Routing:
                  agent_adjacency=True, device=None):
         L.require_gpu()
         self.network = network
+        network._routing = weakref.ref(self)  # Network.randomize_edge_weights delegates here
         self.n_data = n_data
         self.n_env = n_env
         self.env_var = env_var
@@ -158,6 +191,7 @@ class Routing:
         self.info = torch.zeros(n_env, L.GM_INFO_FIELDS, dtype=torch.float64, device=dev)
         self.nbr = torch.zeros(n_env, N, 3, dtype=torch.int32, device=dev)
         self._actions = torch.zeros(n_env, A, dtype=torch.int32, device=dev)
+        self._edge_stats = torch.zeros(n_env, 3, dtype=torch.float64, device=dev)  # randomize_edge_weights
         self.obs_gemm = None  # GEMM-ready env obs copy (enable_gemm_obs)
         self._lazy_obs = False  # kernels write only obs_gemm; obs rows rebuilt on demand (set_lazy_obs)
         self._obs_stale = False
@@ -347,6 +381,22 @@ class Routing:
         with L.timed("shortest_path"):
             L.check(L.lib().gm_policy_shortest_path(self._h, L.ptr(actions), L.stream_ptr(self.device)))
         return actions
+
+    def randomize_edge_weights(self, mode, env_mask=None, **kwargs):
+        """Network.randomize_edge_weights (src/env/network.py:292-351) in every env (env_mask: bool/uint8
+        [n_env] on the device, None = all): "shuffle", "randint" (low=, high=), "bottleneck-971182936" or
+        "set" (edge=(a, b), length=). The env's stream supplies the draws; the shortest paths are solved again
+        and the observation buffers re-emitted with the new lengths. -> float64 [n_env, 3] (host): proportion
+        of the ordered node pairs whose first hop / whole path / path weight changed."""
+        args = edge_change_args(mode, **kwargs)  # an edge the env does not have (a node >= N too) sets nothing
+        m = None if env_mask is None else env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        with L.timed("edge_change"):
+            L.check(L.lib().gm_env_randomize_edge_weights(self._h, *args, L.ptr(m), L.ptr(self._edge_stats),
+                                                          self._stream()))
+            if self._has_state:
+                L.check(L.lib().gm_env_observe(self._h, C.byref(self._obsbufs), self._stream()))
+        self.mark_obs_stale()
+        return self._edge_stats.cpu().numpy()
 
     def get_nodes_adjacency(self):
         out = torch.empty(self.n_env, self.n_nodes, self.n_nodes, dtype=torch.int8, device=self.device)

@@ -39,6 +39,9 @@ class NetMonWrapper:
         need = env.obs_dim + self.graph_features
         if env.obs_stride < need:
             raise ValueError(f"env obs buffer too narrow: create the env with obs_extra={self.graph_features}")
+        self.frozen = False
+        self._tables = []  # unfused road: [h, neighbour h] of this wrapper's last NetMon step
+        self.frozen_steps = 0  # NetMon steps skipped since freeze() (evaluate: the state drift is 0 from the first)
         self.env = env
         self.netmon = netmon
         self.startup_iterations = startup_iterations
@@ -119,8 +122,28 @@ class NetMonWrapper:
         self._gstale = False
         self._dirty = True  # the scratch sits where the materialised observation holds h
 
+    def freeze(self):
+        """Disable message passing for the rest of this episode (src/env/wrapper.py:53-58): no NetMon launch,
+        the state and h_prev tables stay as they are, and agents read them at their current nodes. reset()
+        clears it."""
+        self.frozen = True
+
+    def _frozen_step(self):
+        """src/env/wrapper.py:67-75: only the agent mapping moves. Fused road: the DQN's first GEMM gathers from
+        the state tables through agent_node, which the env step refreshed (and `.obs` re-gathers on a read), so
+        nothing is launched. Unfused road: the agent rows are gathered again from the last readout's tables."""
+        e = self.env
+        self.frozen_steps += 1
+        if self.fused:
+            self._dirty = True
+            return
+        with torch.no_grad():
+            self.netmon.readout_tables(self._tables, e.nbr, e.agent_node, out=e.obs_buf, out_col=e.obs_dim)
+
     def _netmon_step(self):
         e = self.env
+        if self.frozen:
+            return self._frozen_step()
         with torch.no_grad():
             self.last_netmon_state = self.current_netmon_state
             if self.fused:
@@ -139,11 +162,14 @@ class NetMonWrapper:
                 self._dirty = True
             else:
                 self.netmon.state = self.current_netmon_state
-                self.netmon.forward_graph(e.node_obs, e.nbr, e.agent_node, out=e.obs_buf, out_col=e.obs_dim)
+                self.netmon.forward_graph(e.node_obs, e.nbr, e.agent_node, out=e.obs_buf, out_col=e.obs_dim,
+                                          tables=self._tables)  # kept for a frozen step's readout
                 self.current_netmon_state = self.netmon.state
 
     def reset_(self):
         """reset() without materialising the joint observation (the rollout driver's form)."""
+        self.frozen = False
+        self.frozen_steps = 0
         self.current_netmon_state = None
         self.last_netmon_state = None
         self._cur = 1  # the start-up step writes buffer pair 0

@@ -158,6 +158,23 @@ int gm_policy_shortest_path(gm_env* env, int32_t* actions, void* stream);
 /* first-hop table int32 [n_env, N, N]: out[s][t] = next node on the s -> t path (t on the
  * diagonal) — network.shortest_paths[s][t][1] (src/env/network.py:279) */
 int gm_env_first_hops(gm_env* env, int32_t* out, void* stream);
+/* Network.randomize_edge_weights (src/env/network.py:292-351) for every env with env_mask[env] != 0 (NULL: all),
+ * in one launch on `stream`:
+ *   GM_EDGE_SHUFFLE  np.random.shuffle of the env's lengths in edge order,
+ *   GM_EDGE_RANDINT  np.random.randint(low, high) per edge in edge order (1 <= low < high <= 256),
+ *   GM_EDGE_SET      the edge with sorted endpoints (edge_start, edge_end) gets `length` (1..255); an env
+ *                    without that edge (an endpoint outside the graph included) keeps its lengths.
+ * Draws come from the env's own stream and advance it. The shortest paths are solved again on the new lengths
+ * (apsp, and with it gm_env_topology's node_aux, gm_policy_shortest_path, gm_env_first_hops and the step's
+ * distance bookkeeping); packets, loads and visited sets are not touched, and the observation buffers are not
+ * rewritten (gm_env_observe does that). stats: double [n_env, 3] = the proportions of the N (N - 1) ordered
+ * pairs whose first hop / whole path / path weight changed (zeros for an env left out by env_mask). */
+#define GM_EDGE_SHUFFLE 0
+#define GM_EDGE_RANDINT 1
+#define GM_EDGE_SET 2
+int gm_env_randomize_edge_weights(gm_env* env, int32_t mode, int32_t low, int32_t high, int32_t edge_start,
+                                  int32_t edge_end, int32_t length, const uint8_t* env_mask, double* stats,
+                                  void* stream);
 /* Switch the topology source between resets (the reference's evaluation sets
  * network.seeds = EVAL_SEEDS and sequential_topology_seeds = True, src/main.py:553-560,
  * 1049-1053). The sequential index restarts at 0 (network.py:87); with interleave, env b
